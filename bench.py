@@ -6,7 +6,12 @@ forward, RFB discriminator on hr and sr, VGG19 perceptual + relativistic adversa
 AdamW_G), then the discriminator pass (fresh G forward, D on hr and sr.detach(), D backward, AdamW_D) and both
 OneCycleLR steps -- with the RRDB generator (nf 64, nb 11, gc 16; conf/generator/esrgan.yaml), per-GPU batch
 32, bf16 MFMA compute, fp32 master weights / optimiser state.  Each step segment is captured once as a hipGraph
-and replayed.  The config-2 L1 pre-training step is measured in the same run and reported as ``config2``.
+and replayed.
+
+A plain run (``--gpus 1 --steps K --warmup W``) sets up, warms up, times the K steps and prints the result line;
+``--dump-outputs DIR`` also writes the last timed step's outputs as ``DIR/<name>.npy``.  ``--full`` adds, in the same
+run, the per-step median, the per-kernel timing and roofline, the CPU baseline and the config-2 L1 pre-training step
+(reported as ``config2``); without it those fields of the line are null or empty.
 
 Multi-GPU: ``--gpus N`` launches N ranks itself (one process per GPU, RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_ADDR=127.0.0.1 / MASTER_PORT in each child's environment; the launcher never touches the GPU) unless a
@@ -41,8 +46,15 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: per-step median, the config-2 sub-record, "
+                         "per-kernel timing / roofline and the CPU baseline (each can be switched off with its --no-* "
+                         "option).  Without --full the run only sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (losses, the generator's SR "
+                         "output, the updated fp32 parameters) as DIR/<name>.npy, float32")
     ap.add_argument("--median-steps", type=int, default=50,
-                    help="extra steps timed one by one (HIP events) after the timed loop: median per-step time")
+                    help="--full: extra steps timed one by one (HIP events) after the timed loop: median per-step time")
     ap.add_argument("--batch", type=int, default=32, help="per-GPU batch")
     ap.add_argument("--lr-size", type=int, default=64)
     ap.add_argument("--nb", type=int, default=11)
@@ -140,6 +152,25 @@ def cpu_info():
         pass
     return {"cpu_model": model, "affinity_cores": aff, "cgroup_quota_cores": quota,
             "threads": min(aff, quota) if quota else aff}
+
+
+DUMP_MAX_ELEMS = 1 << 21  # per array: 8 MB of float32 (the headline run's SR batch, 32 x 256 x 256, fits whole)
+
+
+def dump_outputs(dirname, arrays):
+    """``--dump-outputs``: write each tensor of ``arrays`` as ``dirname/<name>.npy`` (float32, C order).  An array of
+    more than DUMP_MAX_ELEMS elements is stored as a fixed sample of that many of its flattened elements: sorted
+    indices drawn once from PCG64(crc32(name)), so two builds store the same positions."""
+    import zlib
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            rng = np.random.Generator(np.random.PCG64(zlib.crc32(name.encode("utf-8"))))
+            idx = np.sort(rng.integers(0, t.numel(), size=DUMP_MAX_ELEMS, dtype=np.int64))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(t.float().cpu().numpy()))
 
 
 def pmc_traffic(kernel, mode):
@@ -369,8 +400,10 @@ def run_infer(args, world, rank, dev):
             elapsed = float(tt.item())
         ms = elapsed / args.steps * 1e3
         mpix = world * hh * ww / 1e6 / (elapsed / args.steps)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"sr": out["sr"]})
         roof, kern = None, {}
-        if not args.no_kernel_timing:
+        if args.full and not args.no_kernel_timing:
             timer = KernelTimer()
             ops.PROFILER = timer
             fwd()
@@ -386,7 +419,7 @@ def run_infer(args, world, rank, dev):
                     for k, v in sorted(agg.items(), key=lambda kv: -kv[1][1])}
             flop_fwd = sum(v[2] for v in agg.values())
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline_infer(args, {k: v.detach().cpu().float() for k, v in net.state_dict().items()})
     if rank == 0:
         res = {
@@ -475,6 +508,7 @@ def build_train(args, mode, world, dev):
     lr = torch.cat([t, e, m], 1)[:, :, ::4, ::4].contiguous()
     batch = {k: v.to(dev) for k, v in {"lr": lr, "hr": t, "elevation": e, "mask": m}.items()}
     loss_buf = torch.zeros(2, device=dev)
+    last = {}  # the generator output of the newest forward (--dump-outputs); a captured segment rewrites it in place
 
     def toggle(net_on):
         for net in (g, d):
@@ -486,6 +520,7 @@ def build_train(args, mode, world, dev):
             for p in g.parameters():
                 p.grad = None  # zero_grad(set_to_none=True): backward overwrites the flat grad buffer
             sr = g(batch["lr"], batch["elevation"], batch["mask"])
+            last["sr"] = sr.detach()
             loss = l1_loss(sr, batch["hr"])
             loss.backward()
             loss_buf[0].copy_(loss.detach())
@@ -507,12 +542,13 @@ def build_train(args, mode, world, dev):
             for p in d.parameters():
                 p.grad = None
             _hr, sr = task.common_step(batch)
+            last["sr"] = sr.detach()
             ld = task.loss_d(batch["hr"], sr)
             ld.backward()
             loss_buf[1].copy_(ld.detach())
 
         segments = [(seg_g, g), (seg_d, d), (opt_d.step, None)]
-    return dict(g=g, d=d, segments=segments, loss_buf=loss_buf, B=B, hr=hr, lr_size=lr_size, batch=batch)
+    return dict(g=g, d=d, segments=segments, loss_buf=loss_buf, B=B, hr=hr, lr_size=lr_size, batch=batch, last=last)
 
 
 def make_runner(w, world, dev, use_graph=True):
@@ -614,9 +650,10 @@ def make_runner(w, world, dev, use_graph=True):
     return dict(run=run, step_eager=step_eager, graphs=graphs, overlap=overlap)
 
 
-def measure_train(args, mode, world, rank, dev, kernel_timing=True):
+def measure_train(args, mode, world, rank, dev, kernel_timing=True, median_steps=0, dump=None):
     """Capture the step of ``mode`` (hipGraph segments), run W warm-up steps, time exactly K steps between a barrier +
-    synchronize on both sides (max over ranks), then ``median_steps`` more steps one HIP-event pair each."""
+    synchronize on both sides (max over ranks), write the last timed step's outputs to ``dump`` if given, then
+    ``median_steps`` more steps one HIP-event pair each and (``kernel_timing``) the per-kernel profile of one eager step."""
     from climsr_amd import ops
 
     w = build_train(args, mode, world, dev)
@@ -650,18 +687,23 @@ def measure_train(args, mode, world, rank, dev, kernel_timing=True):
     elapsed = max_over_ranks(time.perf_counter() - t0)
     ms = elapsed / args.steps * 1e3
     mpix = world * B * hr * hr / 1e6 / (elapsed / args.steps)
+    if dump and rank == 0:  # what a caller of the timed step holds after its last call
+        arrays = {"loss": loss_buf if mode == "gan" else loss_buf[:1], "sr": w["last"]["sr"], "generator_params": w["g"]._flat}
+        if w["d"] is not None:
+            arrays["discriminator_params"] = w["d"]._flat
+        dump_outputs(dump, arrays)
 
     med = None
-    if args.median_steps > 0:  # per-step HIP events on the replay stream, back to back
-        evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.median_steps + 1)]
+    if median_steps > 0:  # per-step HIP events on the replay stream, back to back
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(median_steps + 1)]
         evs[0].record()
-        for i in range(args.median_steps):
+        for i in range(median_steps):
             run()
             evs[i + 1].record()
         torch.cuda.synchronize()
-        per = [evs[i].elapsed_time(evs[i + 1]) for i in range(args.median_steps)]
+        per = [evs[i].elapsed_time(evs[i + 1]) for i in range(median_steps)]
         med_ms = max_over_ranks(statistics.median(per))
-        med = {"steps": args.median_steps, "after_warmup_steps": args.warmup + args.steps, "ms_per_step": round(med_ms, 3),
+        med = {"steps": median_steps, "after_warmup_steps": args.warmup + args.steps, "ms_per_step": round(med_ms, 3),
                "value": round(world * B * hr * hr / 1e6 / (med_ms / 1e3), 3), "min_ms": round(min(per), 3),
                "max_ms": round(max(per), 3), "source": "per-step HIP events (median over steps, max over ranks)"}
     loss_val = [float(v) for v in loss_buf.cpu()]
@@ -742,15 +784,20 @@ def main(argv=None):
 
     if args.mode == "infer":
         return run_infer(args, world, rank, dev)
-    rec = measure_train(args, args.mode, world, rank, dev, kernel_timing=not args.no_kernel_timing)
+    # a plain run measures the headline step only; --full adds the median steps, the per-kernel profile, config 2 and
+    # the CPU baseline
+    kernel_timing = args.full and not args.no_kernel_timing
+    median_steps = args.median_steps if args.full else 0
+    rec = measure_train(args, args.mode, world, rank, dev, kernel_timing=kernel_timing, median_steps=median_steps,
+                        dump=args.dump_outputs)
     sub = None
-    if args.mode == "gan" and not args.no_config2:
-        r2 = measure_train(args, "pretrain", world, rank, dev, kernel_timing=not args.no_kernel_timing)
+    if args.full and args.mode == "gan" and not args.no_config2:
+        r2 = measure_train(args, "pretrain", world, rank, dev, kernel_timing=kernel_timing, median_steps=median_steps)
         sub = {"metric": "HR MPix/s per training step (4x SR, 64->256 tiles)", "workload": WORKLOAD["pretrain"],
                "value": round(r2["mpix"], 3), "ms_per_step": round(r2["ms"], 3), "median": r2["median"],
                "step_mfma": r2["step_mfma"], "roofline": r2.get("roofline"), "loss_last": r2["loss_last"]}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, rec["hr"], args.mode)
 
     if rank == 0:
