@@ -53,8 +53,23 @@ struct WrArgs {
 typedef uint32_t v2u32 __attribute__((ext_vector_type(2)));
 typedef uint32_t v4u32 __attribute__((ext_vector_type(4)));
 
-template <int EP>
+// EP 1's x * alpha + beta * r, pinned.  Left to -ffp-contract=fast, hipcc fused elements 0..2 of a fragment (one fma
+// onto the rounded beta * r) and, having packed element 3's two products into one v_pk_mul, left that one unfused (both
+// products rounded, then added): which form an element got depended on how the code around it was vectorised.  The
+// forms are stated here so that a change to the epilogue's structure cannot move a result bit.
+__device__ __forceinline__ float wr_axpby(bool fused, float x, float alpha, float beta, float r) {  // fused: a constant once unrolled
+#pragma clang fp contract(off)
+  const float br = beta * r;
+  if (fused) return __builtin_fmaf(x, alpha, br);
+  const float xa = x * alpha;
+  return xa + br;
+}
+
+// ACT = the activation kind (WrArgs::act), resolved by the host: as a run-time field it was tested per accumulator element
+// and hipcc kept a uniform branch tree around each of the 64 elements of a lane
+template <int EP, int ACT>
 __global__ __launch_bounds__(256, 1) void conv_wr_kernel(WrArgs a) {
+  static_assert(EP == 2 ? (ACT == 3 || ACT == 4) : EP == 1 ? ACT == 0 : (ACT >= 0 && ACT <= 2), "conv_wr_ep()'s pairs");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // vector-memory operations of one epilogue (loads + stores), fixed per lane
   constexpr int NEPI = EP == 0 ? 16 : (EP == 3 || EP == 4 ? 17 : 32);
@@ -97,22 +112,48 @@ __global__ __launch_bounds__(256, 1) void conv_wr_kernel(WrArgs a) {
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(off), "s"(xr), "s"(lds) : "memory");
   };
-  auto decode = [&](int tile, int& nimg, int& oy0, int& ox0) {
-    const int tx = tile % a.tiles_x, r = tile / a.tiles_x, ty = r % a.tiles_y;
-    nimg = r / a.tiles_y;
-    oy0 = ty * WR_TR;
-    ox0 = tx * WR_TC;
-  };
-  auto issue = [&](int tile, int b) {  // tile < 0: zeros (keeps the per-iteration DMA count fixed)
-    int nimg = 0, oy0 = -1 << 20, ox0 = 0;
-    if (tile >= 0) decode(tile, nimg, oy0, ox0);
-    const uint32_t dst = mybuf + (uint32_t)(b * WR_BUF);
+  // interior tiles of a non-upsampled input (the whole 6 x 18 footprint inside the image, a wave-uniform test): slot
+  // (pixel (py, px), c)'s source offset is the footprint corner's (scalar, per tile) + this per-lane constant -- one
+  // v_add per DMA instruction instead of the decode / bounds tests / 64-bit address chain of the border path.  Pad
+  // slots: BUF_OOB + corner stays out of range (corner < x_bytes < 2^31, so the sum neither wraps nor re-enters).
+  uint32_t lc[WR_NI];
 #pragma unroll
-    for (int i = 0; i < WR_NI; ++i) {
-      const int iy = oy0 - 1 + (dg[i] >> 16), ix = ox0 - 1 + ((dg[i] >> 8) & 255), c = dg[i] & 255;
-      const bool ok = dg[i] >= 0 && iy >= 0 && iy < lh && ix >= 0 && ix < lw;
-      const uint32_t off = (uint32_t)((((long)(nimg * a.in_h + (iy >> ups)) * a.in_w + (ix >> ups)) * a.in_cs + a.in_co + c * 8) * 2);
-      glds(ok ? off : BUF_OOB, dst + (uint32_t)(i * 1024));
+  for (int i = 0; i < WR_NI; ++i)
+    lc[i] = dg[i] >= 0 ? (uint32_t)((((dg[i] >> 16) * a.in_w + ((dg[i] >> 8) & 255)) * a.in_cs + (dg[i] & 255) * 8) * 2) : BUF_OOB;
+  // a tile as (tx, ty, image): decoded once per wave, then advanced by the decomposition of the stride G4 to the
+  // wave's next tile (no division per tile)
+  int tx, ty, ni;
+  {
+    const int r = T / a.tiles_x;
+    tx = T - r * a.tiles_x;
+    ni = r / a.tiles_y;
+    ty = r - ni * a.tiles_y;
+  }
+  const int g4r = G4 / a.tiles_x, dtx = G4 - g4r * a.tiles_x, dni = g4r / a.tiles_y, dty = g4r - dni * a.tiles_y;
+  auto advance = [&](int& x, int& y, int& n) {  // dtx < tiles_x, dty < tiles_y: one carry each
+    x += dtx;
+    int cy = x >= a.tiles_x ? 1 : 0;
+    x -= cy ? a.tiles_x : 0;
+    y += dty + cy;
+    cy = y >= a.tiles_y ? 1 : 0;
+    y -= cy ? a.tiles_y : 0;
+    n += dni + cy;
+  };
+  auto issue = [&](bool live, int ttx, int tty, int nimg, int b) {  // !live: zeros (keeps the per-iteration DMA count fixed)
+    const int oy0 = live ? tty * WR_TR : -1 << 20, ox0 = ttx * WR_TC;
+    const uint32_t dst = mybuf + (uint32_t)(b * WR_BUF);
+    if (live && ups == 0 && oy0 >= 1 && oy0 + WR_TR < a.in_h && ox0 >= 1 && ox0 + WR_TC < a.in_w) {
+      const uint32_t corner = (uint32_t)((((nimg * a.in_h + oy0 - 1) * a.in_w + ox0 - 1) * a.in_cs + a.in_co) * 2);
+#pragma unroll
+      for (int i = 0; i < WR_NI; ++i) glds(lc[i] + corner, dst + (uint32_t)(i * 1024));
+    } else {
+#pragma unroll
+      for (int i = 0; i < WR_NI; ++i) {
+        const int iy = oy0 - 1 + (dg[i] >> 16), ix = ox0 - 1 + ((dg[i] >> 8) & 255), c = dg[i] & 255;
+        const bool ok = dg[i] >= 0 && iy >= 0 && iy < lh && ix >= 0 && ix < lw;
+        const uint32_t off = (uint32_t)((((long)(nimg * a.in_h + (iy >> ups)) * a.in_w + (ix >> ups)) * a.in_cs + a.in_co + c * 8) * 2);
+        glds(ok ? off : BUF_OOB, dst + (uint32_t)(i * 1024));
+      }
     }
   };
 
@@ -120,10 +161,12 @@ __global__ __launch_bounds__(256, 1) void conv_wr_kernel(WrArgs a) {
   const __amdgpu_buffer_rsrc_t pr = buf_rsrc(a.ch_part, SUMS && a.ch_part ? (uint32_t)a.ntiles * 256u : 0u);
   const __amdgpu_buffer_rsrc_t rr = buf_rsrc(a.res1, (EP == 1 || EP == 2) ? a.r1_bytes : 0u);
   const int lb = col * WR_XP * 2 + g * 16;  // this lane's byte offset in a footprint row: pixel col, channels 8 g ..
-  issue(T, 0);
+  issue(true, tx, ty, ni, 0);
   for (int it = 0;; ++it) {
     const int Tn = T + G4;
-    issue(Tn < a.ntiles ? Tn : -1, (it + 1) & 1);
+    int txn = tx, tyn = ty, nin = ni;
+    advance(txn, tyn, nin);
+    issue(Tn < a.ntiles, txn, tyn, nin, (it + 1) & 1);
     // tile T's footprint has landed once at most the younger operations are outstanding: the last epilogue's and
     // the DMA just issued
     if (it == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WR_NI) : "memory");
@@ -152,8 +195,7 @@ __global__ __launch_bounds__(256, 1) void conv_wr_kernel(WrArgs a) {
     pad_mfma16(acc);
     // ---- epilogue straight from the accumulators: lane (col, g) holds co 16 t + 4 g .. + 3 of pixel (m, col);
     // every lane issues the same number of loads / stores (out-of-range offsets are dropped)
-    int nimg, oy0, ox0;
-    decode(T, nimg, oy0, ox0);
+    const int nimg = ni, oy0 = ty * WR_TR, ox0 = tx * WR_TC;
     const int ox = ox0 + col;
     uint32_t off[4];
     uint2 rv[4][4];
@@ -184,14 +226,14 @@ __global__ __launch_bounds__(256, 1) void conv_wr_kernel(WrArgs a) {
           if constexpr (EP == 2) {
             const uint32_t w = i < 2 ? rv[m][t].x : rv[m][t].y;
             const float r = __uint_as_float((i & 1) ? (w & 0xFFFF0000u) : (w << 16));
-            x = r > 0.f ? x : (a.act == 3 ? x * a.slope : 0.f);
+            x = r > 0.f ? x : (ACT == 3 ? x * a.slope : 0.f);
           } else {
-            if (a.act == 1) x = x > 0.f ? x : x * a.slope;
-            else if (a.act == 2) x = x > 0.f ? x : 0.f;
+            if constexpr (ACT == 1) x = x > 0.f ? x : x * a.slope;
+            else if constexpr (ACT == 2) x = x > 0.f ? x : 0.f;
             if constexpr (EP == 1) {
               const uint32_t w = i < 2 ? rv[m][t].x : rv[m][t].y;
               const float r = __uint_as_float((i & 1) ? (w & 0xFFFF0000u) : (w << 16));
-              x = x * a.alpha1 + a.beta1 * r;
+              x = wr_axpby(i < 3, x, a.alpha1, a.beta1, r);
             }
           }
           v[i] = x;
@@ -229,6 +271,7 @@ __global__ __launch_bounds__(256, 1) void conv_wr_kernel(WrArgs a) {
     }
     if (Tn >= a.ntiles) break;
     T = Tn;
+    tx = txn; ty = tyn; ni = nin;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the zero-filling DMA past the last tile lands before the wave ends
 }
@@ -293,8 +336,17 @@ int conv_wr_launch(const ClimsrConvDesc* d, const ClimsrEpilogue* ep, const uint
   a.r1_bytes = res ? (uint32_t)(opx * ep->res1_cstride * 2) : 0u;
   const int ncu = device_cus();
   const int grid = std::min(ceil_div(a.ntiles, 4), ncu);
-  void (*k)(WrArgs) = epk == 0 ? conv_wr_kernel<0> : epk == 1 ? conv_wr_kernel<1> : epk == 2 ? conv_wr_kernel<2>
-                      : epk == 3 ? conv_wr_kernel<3> : conv_wr_kernel<4>;
+  // (conv_wr_ep() admits act 0..2 for EP 0 / 3 / 4, 0 for EP 1, 3 / 4 for EP 2)
+  void (*k)(WrArgs) = nullptr;
+#define WR_ACT3(E) (a.act == 1 ? conv_wr_kernel<E, 1> : a.act == 2 ? conv_wr_kernel<E, 2> : conv_wr_kernel<E, 0>)
+  switch (epk) {
+    case 0: k = WR_ACT3(0); break;
+    case 1: k = conv_wr_kernel<1, 0>; break;
+    case 2: k = a.act == 3 ? conv_wr_kernel<2, 3> : conv_wr_kernel<2, 4>; break;
+    case 3: k = WR_ACT3(3); break;
+    default: k = WR_ACT3(4); break;
+  }
+#undef WR_ACT3
   const int lds = (epk == 3 || epk == 4) ? WR_LDS_ALL : WR_LDS;
   if (int e = lds_opt_in((const void*)k, WR_LDS_ALL)) return e;
   hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, s, a);

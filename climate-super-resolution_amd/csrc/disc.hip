@@ -214,11 +214,13 @@ __global__ __launch_bounds__(256) void bn_finish_stats_kernel(const double* __re
 
 // y = act(z * scale + shift) with scale = gamma*rstd, shift = beta - mean*scale (mode 0: batch statistics
 // mean/rstd; mode 1: running statistics, rstd = rsqrt(var + eps)).
-template <int MODE>
+// ACT = the activation kind, resolved by the host (bn_apply_launch): as a run-time argument hipcc kept a branch tree
+// around each of the 8 elements of a pixel, in all five copies of the pixel body.
+template <int MODE, int ACT>
 __global__ __launch_bounds__(256) void bn_apply_kernel(int npix, int c, int per_blk, const uint16_t* __restrict__ z,
                                                        const float* __restrict__ mean, const float* __restrict__ var_or_rstd,
                                                        float eps, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                       int act, float slope, uint16_t* __restrict__ y) {
+                                                       float slope, uint16_t* __restrict__ y) {
   const int G = c >> 3;
   const int R = 256 / G;
   const int cg = threadIdx.x % G;
@@ -239,7 +241,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(int npix, int c, int per_
     const size_t off = (size_t)p * c + cg * 8;
     unpack8(*(const uint4*)(z + off), f);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) f[i] = act_apply(fmaf(f[i], sc[i], sh[i]), act, slope);
+    for (int i = 0; i < 8; ++i) f[i] = act_apply(fmaf(f[i], sc[i], sh[i]), ACT, slope);
     *(uint4*)(y + off) = pack8(f);
   };
   int p = p0 + r;
@@ -333,6 +335,16 @@ static inline int bn_apply_grid(long npix, int c, int* per_blk) {
   return ceil_div(npix, *per_blk);
 }
 
+// y = act(BN(z)) over npix pixels; any act other than 1 / 2 is the identity, as in act_apply()
+template <int MODE>
+static void bn_apply_launch(hipStream_t s, int64_t npix, int c, const uint16_t* z, const float* mean, const float* var_or_rstd, float eps,
+                            const float* gamma, const float* beta, int act, float slope, uint16_t* y) {
+  int per;
+  const int nb = bn_apply_grid(npix, c, &per);
+  auto k = act == 1 ? bn_apply_kernel<MODE, 1> : act == 2 ? bn_apply_kernel<MODE, 2> : bn_apply_kernel<MODE, 0>;
+  hipLaunchKernelGGL(k, dim3(nb), dim3(256), 0, s, (int)npix, c, per, z, mean, var_or_rstd, eps, gamma, beta, slope, y);
+}
+
 static bool bn_shape_ok(int64_t npix, int c) { return c > 0 && c % 8 == 0 && c <= 2048 && npix > 0 && npix * (int64_t)c < (1ll << 31); }
 
 }  // namespace
@@ -355,10 +367,7 @@ extern "C" int climsr_bn_forward(const uint16_t* z, int64_t npix, int c, const f
                      nullptr, nullptr, nullptr, nullptr, 0.f, workspace);
   hipLaunchKernelGGL(bn_finish_stats_kernel, dim3(ceil_div(c, 8)), dim3(256), 0, s, workspace, g.parts, c, (int)npix, eps,
                      momentum, mean, rstd, run_mean, run_var, num_batches_tracked);
-  int per;
-  const int nb = bn_apply_grid(npix, c, &per);
-  hipLaunchKernelGGL(bn_apply_kernel<0>, dim3(nb), dim3(256), 0, s, (int)npix, c, per, z, mean, rstd, 0.f, gamma, beta, act, slope,
-                     y);
+  bn_apply_launch<0>(s, npix, c, z, mean, rstd, 0.f, gamma, beta, act, slope, y);
   return check_launch("bn_forward");
 }
 
@@ -372,10 +381,7 @@ extern "C" int climsr_bn_forward_parts(const double* parts, int64_t nparts, cons
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(bn_finish_stats_kernel, dim3(ceil_div(c, 8)), dim3(256), 0, s, parts, (int)nparts, c, (int)npix, eps, momentum,
                      mean, rstd, run_mean, run_var, num_batches_tracked);
-  int per;
-  const int nb = bn_apply_grid(npix, c, &per);
-  hipLaunchKernelGGL(bn_apply_kernel<0>, dim3(nb), dim3(256), 0, s, (int)npix, c, per, z, mean, rstd, 0.f, gamma, beta, act, slope,
-                     y);
+  bn_apply_launch<0>(s, npix, c, z, mean, rstd, 0.f, gamma, beta, act, slope, y);
   return check_launch("bn_forward_parts");
 }
 
@@ -385,10 +391,7 @@ extern "C" int climsr_bn_inference(const uint16_t* z, int64_t npix, int c, const
     set_error("bn_inference: bad args");
     return CLIMSR_EINVAL;
   }
-  int per;
-  const int nb = bn_apply_grid(npix, c, &per);
-  hipLaunchKernelGGL(bn_apply_kernel<1>, dim3(nb), dim3(256), 0, (hipStream_t)stream, (int)npix, c, per, z, run_mean, run_var, eps,
-                     gamma, beta, act, slope, y);
+  bn_apply_launch<1>((hipStream_t)stream, npix, c, z, run_mean, run_var, eps, gamma, beta, act, slope, y);
   return check_launch("bn_inference");
 }
 
