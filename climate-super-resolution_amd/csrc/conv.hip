@@ -2248,7 +2248,8 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_s2_kernel(FwdArgs a) {
 static int plain_ep(const FwdArgs& a);
 static bool fwd_s2_shape(const ClimsrConvDesc* d, const FwdArgs& a) {
   return d->stride == 2 && d->ks == 3 && d->pad == 1 && d->up == 1 && d->cc == 32 && d->in_c % 32 == 0 && d->out_c % 64 == 0 &&
-         d->in_coff % 8 == 0 && d->in_cstride % 8 == 0 && a.kcpad == 288 && plain_ep(a) == 8;
+         d->in_coff % 8 == 0 && d->in_cstride % 8 == 0 && a.kcpad == 288 && plain_ep(a) == 8 &&
+         (long)d->n * d->in_h * d->in_w * d->in_cstride * 2 < (1L << 31);  // the kernel's int / 32-bit input offsets
 }
 
 // the LDS-DMA kernel (conv_dma.hip conv_fwd_s2_dma_kernel); the register-staged 8-wave kernel it replaced measured

@@ -476,7 +476,9 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_s2_dma_kernel(FwdArgs a) {
   decode(v, nimg, oy0, ox0, co0, tile);
   offsets(nimg, oy0, ox0, co0);
   // chunks 0 and 1 in flight before the loop; chunk c + 2 (of this item, or of the next one) is requested during chunk
-  // c into the third buffer.  A wave's DMA pieces per chunk: 8 (waves 0, 1), 7 (wave 2), 6 (waves 3-7)
+  // c into the third buffer -- except during the last two chunks of the workgroup's last item, when nothing is left to
+  // request (so its last chunk is awaited with vmcnt(0), below).  A wave's DMA pieces per chunk: 8 (waves 0, 1),
+  // 7 (wave 2), 6 (waves 3-7)
 #pragma unroll
   for (int p = 0; p < 8; ++p) piece(p, 0, 0);
 #pragma unroll
@@ -492,10 +494,14 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_s2_dma_kernel(FwdArgs a) {
 #pragma unroll
       for (int t = 0; t < 4; ++t) acc[m][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int c = 0; c < nch; ++c, cur = cur == 2 ? 0 : cur + 1) {
-      // chunk c has landed once at most the younger requests are outstanding: the next chunk's pieces, and at chunks
-      // 0 / 1 of a later item also the previous item's 8 epilogue stores (issued between them)
+      // chunk c has landed once at most the younger requests are outstanding.  A counted wait names exactly the
+      // requests issued after the awaited one: the next chunk's pieces, and at chunks 0 / 1 of a later item also the
+      // previous item's 8 epilogue stores (issued between them).  The workgroup's very last chunk has no younger
+      // chunk (nothing was requested during chunk nch - 2 of the last item): drain, once per workgroup
       const bool st = c < 2 && v != (int)blockIdx.x;
-      if (npc == 8) {
+      if (c + 1 == nch && vn >= nitem) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      } else if (npc == 8) {
         if (st) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
       } else if (npc == 7) {

@@ -107,6 +107,26 @@ def test_discriminator_bn_conv_routes(routes, stride, cin, cout, hw, want):
     assert last(routes) == want
 
 
+def test_stride2_dma_route_refuses_inputs_past_2gib(routes):
+    """conv_fwd_s2_dma_kernel forms its input offsets in 32 bits (int pixel index, uint32 buffer size): a stride-2
+    64 -> 64 conv at 1024^2 takes it at n=8 (1.07 GB of input) and must not at n=32 (4.3 GB) -- no BatchNorm partial
+    rows are promised for it and the forward falls through to the generic conv."""
+    p = plan(64, 64, 3, 2, bias=False)
+    hw = 1024
+    assert p.bn_parts(64, hw, hw, 32, 64) == 0
+    p.fwd(bf(), 64, 0, hw, hw, bf(), 64, 0, 32, use_bias=False)
+    assert not last(routes).startswith("conv_fwd_s2_dma_kernel"), routes
+    routes.clear()
+    assert p.bn_parts(64, hw, hw, 8, 64) == 8 * (hw // 32) ** 2
+    p.fwd(bf(), 64, 0, hw, hw, bf(), 64, 0, 8, use_bias=False)
+    assert last(routes) == "conv_fwd_s2_dma_kernel<false>"
+    # with partials requested the refused shape is the dispatcher's existing error (the dry run names no kernel),
+    # while the production shapes keep conv_fwd_s2_dma_kernel<true> (test_discriminator_bn_conv_routes)
+    p.fwd(bf(), 64, 0, hw, hw, bf(), 64, 0, 32, use_bias=False, bn_part=torch.empty(1, dtype=torch.float64))
+    assert last(routes) == ""
+    assert b"BatchNorm partials" in _lib.load().climsr_last_error()
+
+
 def _wgrad_name(routes):
     kernels = [r for r in routes if "kernel" in r]
     assert kernels, routes

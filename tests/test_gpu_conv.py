@@ -545,7 +545,9 @@ def test_conv_dgrad_stride2_bf16(cin, cout, h, w, act):
 def test_conv_fwd_stride2_plain_bf16(cin, cout, h, w):
     """The discriminator's stride-2 convs as its forward runs them (rfb_esrgan.py:30-48): no bias, no activation,
     bf16 out for the BatchNorm (conv_fwd_s2_dma_kernel: LDS-DMA, three chunk buffers; ragged 17-row / 10- and 33-column
-    output tiles included) vs F.conv2d in float64 on the same bf16 operands.  Tolerance: bf16 rounding."""
+    output tiles included) vs F.conv2d in float64 on the same bf16 operands.  Tolerance: per element one bf16 rounding
+    (<= 2^-9 relative, 2^-8 allowed) on top of 1e-5 of the scale.  The 96 -> 64 case does not take the LDS-DMA kernel
+    (96 channels pack in 24-channel chunks): it checks the generic stride-2 conv under the same bound."""
     n = 2
     p, wt, _b = make_plan(cin, cout, 3, stride=2, bias=False)
     g = torch.Generator().manual_seed(12)
@@ -556,8 +558,9 @@ def test_conv_fwd_stride2_plain_bf16(cin, cout, h, w):
     torch.cuda.synchronize()
     want = F.conv2d(x.double(), bf(wt).double(), None, stride=2, padding=1)
     got = from_nhwc(y, cout).cpu().double()
-    err = (got - want).abs().max().item()
-    assert err <= 8e-3 * want.abs().max().item() + 1e-6, f"stride-2 fwd max err {err}"
+    scale = want.abs().max().item()
+    err = ((got - want).abs() - want.abs() * 2.0 ** -8).max().item()
+    assert err <= 1e-5 * scale, f"stride-2 fwd: bf16 err {err:.3e} vs scale {scale:.3e}"
 
 
 @pytest.mark.gpu
@@ -612,7 +615,8 @@ WR_CASES = [
     (2, 16, 32, 1, "lrelu"),       # HRconv-like, tile-aligned
     (1, 13, 37, 1, "relu"),        # ragged rows / columns (VGG conv1_2 / RCAB conv1)
     (2, 9, 20, 2, "lrelu"),        # upconv: nearest x2 on load, 18 x 40 output
-    (1, 45, 90, 1, "bias"),        # RCAB conv2 (bias, no activation), several persistent rounds
+    (1, 45, 90, 1, "bias"),        # RCAB conv2 (bias, no activation): 72 wave tiles, one per wave on a 256-CU device
+                                   # (test_gpu_persistent_rounds.py walks several tiles per wave)
     (1, 12, 24, 1, "res"),         # residual epilogue (v * alpha + beta * r)
     (2, 10, 34, 1, "lrelu_bwd"),   # activation backward from the stored activation (HRconv data gradient)
     (1, 7, 16, 1, "relu_bwd"),
