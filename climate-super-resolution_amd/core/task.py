@@ -9,8 +9,12 @@ OneCycleLR(interval="step") per network (task.py:173-226, 53-59).  Subclasses a
 driven by ``climsr_amd.core.trainer.Trainer``.
 
 Divergences (documented in DESIGN.md): the statistics feather read of task.py:146-171 is skipped
-when ``data_path`` has no statistics (synthetic benchmarking); the stand-alone SRCNN
-generator with MSE loss (task.py:141) is outside this build's scope.
+when ``data_path`` has no statistics (synthetic benchmarking).
+
+``generator_type == "srcnn"`` (task.py:141,235-239) selects the stand-alone SRCNN task: the loss is ``MSELoss`` and
+``forward`` hands the generator the batch's ``lr`` alone (data/tile_pipeline.py's "srcnn" batch already carries the
+nearest-upscaled LR tile, elevation and mask as its channels).  Use ``_target_: climsr_amd.models.srcnn.SRCNN`` with
+``in_channels`` 1, 2 or 3.  Every other generator type gets ``L1Loss`` and ``generator(x, elevation, mask)``.
 """
 from __future__ import annotations
 
@@ -21,6 +25,7 @@ import torch
 from torch import Tensor
 
 from ..losses.l1 import L1Loss
+from ..losses.mse import MSELoss
 from ..metrics.sr_metrics import SRMetrics
 from .checkpoint import load_from_checkpoint as _load_from_checkpoint
 from .checkpoint import save_checkpoint as _save_checkpoint
@@ -67,9 +72,8 @@ class TaskSuperResolutionModule(_Base):
             self.hparams = SimpleNamespace(**hp)
         else:  # pragma: no cover
             self.save_hyperparameters(*kwargs.keys())
-        if getattr(self.hparams, "generator_type", "esrgan") == "srcnn":
-            raise NotImplementedError("stand-alone SRCNN + MSE task is outside this build's scope (SURVEY §2)")
-        self.loss = L1Loss()  # task.py:141
+        self._srcnn = getattr(self.hparams, "generator_type", "esrgan") == "srcnn"
+        self.loss = MSELoss() if self._srcnn else L1Loss()  # task.py:141
         self.logged: Dict[str, Tensor] = {}
         zs = dict(getattr(self.hparams, "standardization_stats", None) or {})
         self.metrics = SRMetrics(normalization_method=getattr(self.hparams, "normalization_method", "minmax"),
@@ -86,6 +90,8 @@ class TaskSuperResolutionModule(_Base):
                 self.log(k, v)
 
     def forward(self, x: Tensor, elevation: Tensor = None, mask: Tensor = None) -> Tensor:
+        if self._srcnn:  # task.py:235-239
+            return self.generator(x)
         return self.generator(x, elevation, mask)
 
     def common_step(self, batch: Dict[str, Tensor]) -> Tuple[Tensor, Tensor]:

@@ -299,6 +299,51 @@ extern "C" int climsr_l1_loss_grad(const float* a, const float* b, int64_t n, co
 }
 
 // ------------------------------------------------------------------------------------------
+// MSE loss (mean): the same two-pass tree, differences / squares / partial sums in fp64.  Scalar 4-byte loads
+// (coalesced across the wave), so any n and any 4-byte-aligned pointers work without a head or tail.
+// ------------------------------------------------------------------------------------------
+constexpr int MSE_BLOCKS = 1024;  // = the workspace slots the ABI asks for
+
+__global__ void mse_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, long n, double* ws) {
+  double s = 0.0;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    double d = (double)a[i] - (double)b[i];
+    s += d * d;
+  }
+  double r = block_sum(s);
+  if (threadIdx.x == 0) ws[blockIdx.x] = r;
+}
+
+extern "C" int climsr_mse_loss(const float* a, const float* b, int64_t n, double* workspace, float* out, void* stream) {
+  if (!a || !b || !workspace || !out || n <= 0) {
+    set_error("mse_loss: bad args");
+    return CLIMSR_EINVAL;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int nb = n >= (int64_t)MSE_BLOCKS * 256 ? MSE_BLOCKS : ceil_div(n, 256);
+  hipLaunchKernelGGL(mse_partial_kernel, dim3(nb), dim3(256), 0, s, a, b, (long)n, workspace);
+  hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(256), 0, s, workspace, nb, (long)n, out);
+  return check_launch("mse_loss");
+}
+
+__global__ void mse_grad_kernel(const float* __restrict__ a, const float* __restrict__ b, long n, const float* gscale,
+                                float* __restrict__ ga) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double k = 2.0 * (double)(gscale ? gscale[0] : 1.f) / (double)n;
+  ga[i] = (float)(((double)a[i] - (double)b[i]) * k);
+}
+
+extern "C" int climsr_mse_loss_grad(const float* a, const float* b, int64_t n, const float* gscale, float* ga, void* stream) {
+  if (!a || !b || !ga || n <= 0) {
+    set_error("mse_loss_grad: bad args");
+    return CLIMSR_EINVAL;
+  }
+  hipLaunchKernelGGL(mse_grad_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, a, b, (long)n, gscale, ga);
+  return check_launch("mse_loss_grad");
+}
+
+// ------------------------------------------------------------------------------------------
 // OneCycleLR (torch semantics, cos anneal, beta1 cycling 0.95 <-> 0.85) + AdamW scalars, on device
 // so a captured hipGraph replays the schedule without host round trips.
 // ------------------------------------------------------------------------------------------

@@ -26,7 +26,7 @@ from torch import Tensor
 from ..core.flat import FlatParamsMixin
 from ..ops import (ACT_LRELU, ACT_LRELU_BWD, ACT_NONE, ACT_RELU, ACT_RELU_BWD, OUT_F32, BatchedPacker, ConvPlan, GroupedWgrad, PullPacker, PullPlan,
                    RdbChain, SrcnnTail, Workspace, act_grad, axpby, nchw_to_nhwc, pack_planes8)
-from .srcnn import SRCNN
+from .srcnn import SRCNNParams
 
 
 class ResidualDenseBlock(nn.Module):
@@ -425,7 +425,7 @@ class ESRGANGenerator(FlatParamsMixin, nn.Module):
         self.HRconv = nn.Conv2d(nf, nf, 3, 1, 1, bias=True)
         self.conv_last = nn.Conv2d(nf, out_channels, 3, 1, 1, bias=True)
         self.lrelu = nn.LeakyReLU(negative_slope=0.2, inplace=True)
-        self.srcnn = SRCNN(in_channels=3, out_channels=out_channels)
+        self.srcnn = SRCNNParams(in_channels=3, out_channels=out_channels)
         self._flatten()
         object.__setattr__(self, "_engine", None)
         object.__setattr__(self, "_grad_ready_hook", None)

@@ -28,7 +28,7 @@ from torch import Tensor
 from .. import _lib
 from .._lib import check, ptr
 from ..ops import ACT_RELU, OUT_BF16, OUT_F32, BatchedPacker, ConvPlan, nchw_to_nhwc
-from .srcnn import SRCNN
+from .srcnn import SRCNNParams
 
 
 def default_conv(in_channels: int, out_channels: int, kernel_size: int, bias: bool = True) -> nn.Module:
@@ -95,7 +95,7 @@ class RCAN(nn.Module):
         body.append(conv(n_feats, n_feats, self.kernel_size))
         self.body = nn.Sequential(*body)
         self.tail = nn.Sequential(Upsampler(conv, scaling_factor, n_feats, act=False), conv(n_feats, out_channels, self.kernel_size))
-        self.srcnn = SRCNN(in_channels=3, out_channels=out_channels)
+        self.srcnn = SRCNNParams(in_channels=3, out_channels=out_channels)
         self._engine = None
 
     def load_state_dict(self, state_dict: dict, strict: bool = False):

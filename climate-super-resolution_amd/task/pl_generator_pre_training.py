@@ -3,6 +3,9 @@
 ``GeneratorPreTrainingLightningModule`` is provided as an alias: conf/task/generator_pre_training.yaml:4
 targets that name, which the reference never defines, so with climsr_amd the shipped config
 instantiates.
+
+The loss is the task's: ``L1Loss``, or ``MSELoss`` when ``generator_type == "srcnn"`` (core/task.py; the stand-alone
+``climsr_amd.models.srcnn.SRCNN`` generator, called with the batch's ``lr`` alone).
 """
 from typing import Any
 

@@ -263,6 +263,13 @@ int climsr_l1_loss(const float* a, const float* b, int64_t n, double* workspace,
 /* L1Loss backward: ga = gscale[0] * sign(a-b) / n. */
 int climsr_l1_loss_grad(const float* a, const float* b, int64_t n, const float* gscale, float* ga, void* stream);
 
+/* MSELoss (mean) forward: out[0] = mean((a-b)^2) (deterministic two-pass tree; differences, squares and partial
+ * sums in fp64; no atomics).  workspace >= 1024 doubles.  Any n >= 1, pointers 4-byte aligned.
+ * torch.nn.MSELoss of the SRCNN task (task.py:141). */
+int climsr_mse_loss(const float* a, const float* b, int64_t n, double* workspace, float* out, void* stream);
+/* MSELoss backward: ga[i] = gscale[0] * 2 * (a[i]-b[i]) / n (gscale: device scalar, NULL = 1). */
+int climsr_mse_loss_grad(const float* a, const float* b, int64_t n, const float* gscale, float* ga, void* stream);
+
 /* Device-side OneCycleLR(cos, beta1 cycling) + AdamW bias corrections (torch semantics),
  * state[0] = optimizer step count (as double) incremented here, state[1] = scheduler step.
  * hp out: {lr, beta1, beta2, eps, wd, step_size=lr/bc1, bc2_sqrt, 0}. */
