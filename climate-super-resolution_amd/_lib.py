@@ -155,6 +155,13 @@ SIGNATURES = {
     "climsr_adamw_step": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "climsr_adamw_step_mirror": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                                          c_void_p]),
+    "climsr_adamw_step_scaled": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                         c_void_p, c_void_p]),
+    "climsr_grad_norm_chunk": (c_int64, []),
+    "climsr_grad_norm_workspace": (c_int64, [c_int64, c_int]),
+    "climsr_grad_norm": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p,
+                                 c_void_p]),
+    "climsr_scale_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "climsr_bn_workspace_doubles": (c_int64, [c_int64, c_int]),
     "climsr_bn_forward": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -457,3 +457,62 @@ extern "C" int climsr_adamw_step_mirror(int64_t n, float* p, const float* g, flo
                      (long)mirror_lo, (long)mirror_n);
   return check_launch("adamw_step_mirror");
 }
+
+// The same update reading G = g * gscale[0] (the gradient-clipping coefficient, a device scalar); g is only read.
+// It must be bit-identical to adamw_kernel on a gradient multiplied beforehand in fp32, so nothing here is left to the
+// compiler's contraction: it is off inside adamw_scaled_elem and every fused multiply-add is written out.  They are the
+// ones hipcc forms in adamw_kernel (its ISA): m = fma(1-b1, G-m, m) and p = fma(1-lr*wd, p, -step_size*q) everywhere,
+// but v = fma(1-b2, G*G, b2*v) in the 16-byte path and v = fma(b2, v, (1-b2)*(G*G)) in the tail loop (VEC selects).
+// tests/test_gpu_gradnorm.py holds the two kernels to bit-identity on both paths; if a compiler change moves
+// adamw_kernel's fusions, those tests say so and this function follows.
+template <bool VEC>
+__device__ __forceinline__ void adamw_scaled_elem(float& p, float g, float c, float& m, float& v, float decay, float omb1,
+                                                  float omb2, float b2, float eps, float step_size, float bc2s) {
+#pragma clang fp contract(off)
+  const float G = g * c;  // rounded to fp32 on its own
+  m = fmaf(omb1, G - m, m);
+  v = VEC ? fmaf(omb2, G * G, b2 * v) : fmaf(b2, v, omb2 * (G * G));
+  p = fmaf(decay, p, -(step_size * (m / (sqrtf(v) / bc2s + eps))));
+}
+__global__ void adamw_scaled_kernel(long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                    float* __restrict__ v, const float* __restrict__ hp, const float* __restrict__ gscale,
+                                    uint16_t* __restrict__ mirror, long mlo, long mn) {
+  const float lr = hp[0], b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4], step_size = hp[5], bc2s = hp[6];
+  const float c = gscale[0];
+  const float decay = fmaf(-lr, wd, 1.f), omb1 = 1.f - b1, omb2 = 1.f - b2;
+  long i4 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i4 + 3 < n) {
+    float4 pp = *(float4*)(p + i4), gg = *(const float4*)(g + i4), mm = *(float4*)(m + i4), vv = *(float4*)(v + i4);
+    float* P = (float*)&pp; const float* G = (const float*)&gg; float* M = (float*)&mm; float* V = (float*)&vv;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) adamw_scaled_elem<true>(P[k], G[k], c, M[k], V[k], decay, omb1, omb2, b2, eps, step_size, bc2s);
+    *(float4*)(p + i4) = pp; *(float4*)(m + i4) = mm; *(float4*)(v + i4) = vv;
+    if (mirror && i4 >= mlo && i4 + 3 < mlo + mn && ((i4 - mlo) & 3) == 0) {  // 8 B store of 4 bf16
+      const uint2 pk = make_uint2((uint32_t)f2bf(P[0]) | ((uint32_t)f2bf(P[1]) << 16), (uint32_t)f2bf(P[2]) | ((uint32_t)f2bf(P[3]) << 16));
+      *(uint2*)(mirror + (i4 - mlo)) = pk;
+    } else if (mirror) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) adamw_mirror(i4 + k, P[k], mirror, mlo, mn);
+    }
+  } else {
+    for (long i = i4; i < n; ++i) {
+      float pi = p[i], mi = m[i], vi = v[i];
+      adamw_scaled_elem<false>(pi, g[i], c, mi, vi, decay, omb1, omb2, b2, eps, step_size, bc2s);
+      p[i] = pi; m[i] = mi; v[i] = vi;
+      adamw_mirror(i, pi, mirror, mlo, mn);
+    }
+  }
+}
+
+extern "C" int climsr_adamw_step_scaled(int64_t n, float* p, const float* g, float* m, float* v, const float* hp,
+                                        const float* gscale, int64_t mirror_lo, int64_t mirror_n, uint16_t* mirror, void* stream) {
+  if (!p || !g || !m || !v || !hp || !gscale || n <= 0 ||
+      (mirror && (mirror_lo < 0 || mirror_n <= 0 || mirror_lo + mirror_n > n))) {
+    set_error("adamw_step_scaled: bad args");
+    return CLIMSR_EINVAL;
+  }
+  long threads = (n + 3) / 4;
+  hipLaunchKernelGGL(adamw_scaled_kernel, dim3(ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream, (long)n, p, g, m, v, hp,
+                     gscale, mirror, mirror ? (long)mirror_lo : 0L, mirror ? (long)mirror_n : 0L);
+  return check_launch("adamw_step_scaled");
+}

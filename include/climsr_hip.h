@@ -281,6 +281,28 @@ int climsr_adamw_step(int64_t n, float* p, const float* g, float* m, float* v, c
  * weight inside the flat buffer: the RFB discriminator's fc.0, rfb_esrgan.py:56-61). */
 int climsr_adamw_step_mirror(int64_t n, float* p, const float* g, float* m, float* v, const float* hp, int64_t mirror_lo,
                              int64_t mirror_n, uint16_t* mirror, void* stream);
+/* The same update on G = g * gscale[0] (device scalar; the product rounded to fp32 before use): bit-identical to
+ * climsr_adamw_step / _mirror fed a gradient pre-multiplied in fp32, and to them as they stand when gscale[0] == 1.
+ * g is not modified.  mirror may be NULL (then mirror_lo / mirror_n are ignored). */
+int climsr_adamw_step_scaled(int64_t n, float* p, const float* g, float* m, float* v, const float* hp, const float* gscale,
+                             int64_t mirror_lo, int64_t mirror_n, uint16_t* mirror, void* stream);
+
+/* ---------------- gradient norms / clipping over a flat gradient buffer (gradnorm.hip) ---------------- */
+
+/* Elements one work item of climsr_grad_norm reduces (a segment of len elements takes ceil(len / chunk) items). */
+int64_t climsr_grad_norm_chunk(void);
+/* Bytes of workspace climsr_grad_norm needs for n elements in nseg segments (monotone in both). */
+int64_t climsr_grad_norm_workspace(int64_t n, int32_t nseg);
+/* Segmented norm of g[0, n): seg_off (device) holds nseg + 1 ascending element offsets, [0] = 0, [nseg] = n; a segment
+ * may start at any element.  kind 0: L2 (squares and sums in fp64; norms[s] = sqrt(sum_s), norms[nseg] =
+ * sqrt(sum of the segment sums)); kind 1: inf (max |g|, a NaN propagates).  clip[0] = (float)min(1, max_norm /
+ * (total + 1e-6)) (torch.nn.utils.clip_grad_norm_; exactly 1 when max_norm <= 0; NaN / 0 for a NaN / infinite total),
+ * clip[1] = 1 iff the total is finite.  Three launches whatever nseg, no atomics, fixed summation order (bit-identical
+ * on a rerun), no host read and no allocation: safe inside a stream capture. */
+int climsr_grad_norm(const float* g, int64_t n, const int64_t* seg_off, int32_t nseg, int32_t kind, double max_norm,
+                     void* workspace, double* norms, float* clip, void* stream);
+/* g[i] *= coef[0] in place (coef: device scalar). */
+int climsr_scale_f32(float* g, int64_t n, const float* coef, void* stream);
 
 /* ---------------- discriminator / perceptual loss / GAN loss (disc.hip) ---------------- */
 
