@@ -1,4 +1,5 @@
-"""RCAN generator (drop-in for ``climsr.models.rcan.RCAN``) -- native inference.
+"""RCAN generator (drop-in for ``climsr.models.rcan.RCAN``): ``RCAN`` is native inference,
+``TrainableRCAN`` is native training; checkpoints are interchangeable.
 
 Same constructor kwargs (``n_resgroups, n_resblocks, n_feats, reduction, scaling_factor, in_channels,
 out_channels, conv, **kwargs``; rcan.py:138-150), same submodule tree and ``state_dict`` keys
@@ -12,14 +13,25 @@ NHWC activations, fp32 accumulation), the residual stream in fp32 with a bf16 sh
 conv, channel attention as ``climsr_channel_attention`` + ``climsr_ca_scale_add`` (pool, 1x1-ReLU-1x1-
 sigmoid, ``x * y + x`` in one pass), the group / body skips fused into the conv epilogues, the
 Upsampler's ``nn.PixelShuffle`` as ``climsr_pixel_shuffle_bf16`` (bit-exact index map) and the SRCNN
-tail as in the ESRGAN generator.  Inference only: the reference runs RCAN from ``inference.py`` with
+tail as in the ESRGAN generator.  ``RCAN`` is inference only: the reference runs it from ``inference.py`` with
 ``net.eval()``; calling it in training mode with gradients enabled raises (no silent non-training).
+
+``TrainableRCAN(FlatParamsMixin, RCAN)`` trains (``_target_: climsr_amd.models.rcan.TrainableRCAN`` with
+``generator_type: "rcan"``; the reference's rcan_pre_training / rcan_fine_tuning experiments): same constructor
+kwargs, submodule tree, ``state_dict`` keys, lenient ``load_state_dict`` and ``forward(x, elev, mask)``, so a checkpoint
+saved from one class loads into the other.  Its parameters live in one flat fp32 buffer (core/flat.py: the fused
+AdamW, both gradient routes, ``set_grad_ready_hook`` with one bucket).  Under ``no_grad`` its forward is the inference
+path above, bit for bit; with gradients the same launches also keep what the backward reads (per RCAB the block input,
+the post-ReLU ``t``, ``u``, the attention scale and the pooled mean behind it).  The backward walks rcan.py:181-192 in
+reverse on the existing conv gradient calls plus ``climsr_channel_attention_bwd`` and ``climsr_pixel_unshuffle_bf16``
+(DESIGN.md §3.9).  It covers ``out_channels == 1``, ``n_feats == 64``, ``in_channels <= 4`` and ``scaling_factor`` 2
+or 4; other values raise ``NotImplementedError`` from the constructor, as does a gradient w.r.t. an input.
 """
 from __future__ import annotations
 
 import logging
 import math
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -27,7 +39,9 @@ from torch import Tensor
 
 from .. import _lib
 from .._lib import check, ptr
-from ..ops import ACT_RELU, OUT_BF16, OUT_F32, BatchedPacker, ConvPlan, nchw_to_nhwc
+from ..core.flat import FlatParamsMixin
+from ..ops import (ACT_NONE, ACT_RELU, ACT_RELU_BWD, OUT_BF16, OUT_F32, BatchedPacker, ConvPlan, SrcnnTail, Workspace, _launch, act_grad,
+                   axpby, nchw_to_nhwc)
 from .srcnn import SRCNNParams
 
 
@@ -135,6 +149,10 @@ class RCAN(nn.Module):
 
 
 class _RcanEngine:
+    def _need_t(self, name: str) -> bool:
+        """Whether conv ``name`` needs its transposed (data-gradient) weight layout: never for inference."""
+        return False
+
     def __init__(self, m: RCAN):
         self.m = m
         self.device = m.head[0].weight.device
@@ -147,7 +165,7 @@ class _RcanEngine:
         for name, mod in mods.items():
             if isinstance(mod, nn.Conv2d) and ".conv_du." not in name:
                 p = ConvPlan(mod.in_channels, mod.out_channels, mod.kernel_size[0], mod.stride[0], mod.padding[0], name)
-                p.bind(mod.weight, mod.bias, need_t=False)
+                p.bind(mod.weight, mod.bias, need_t=self._need_t(name))
                 self.plans[name] = p
         self.ups: List[Tuple[str, int]] = []  # (conv name, shuffle factor)
         up = m.tail[0]
@@ -166,12 +184,18 @@ class _RcanEngine:
         if v != self.version:
             for name, p in self.plans.items():  # rebind in case parameters were replaced
                 mod = self.mods[name]
-                p.bind(mod.weight, mod.bias, need_t=False)
+                p.bind(mod.weight, mod.bias, need_t=self._need_t(name))
             self.packer = BatchedPacker(list(self.plans.values()), self.device)
             self.packer.run()
             self.version = v
 
     def forward(self, x: Tensor, elev: Tensor, mask: Tensor) -> Tensor:
+        return self.run(x, elev, mask, keep=False)[0]
+
+    def run(self, x: Tensor, elev: Tensor, mask: Tensor, keep: bool):
+        """(output, saved activations or None).  keep=False is the inference path.  keep=True (training) computes the
+        same values with the same launches, except that every buffer the backward reads is a fresh one instead of a
+        reused one, and the attention also hands out its pooled mean."""
         m, P, nf = self.m, self.plans, self.nf
         n, cin, h, w = x.shape
         dev = x.device
@@ -204,23 +228,50 @@ class _RcanEngine:
         # u (the RCAB body's output) in bf16 when the conv pools it itself: the attention's mean comes from the fp32
         # values in the epilogue, only the scale-add reads u (half the bytes of the fp32 round trip)
         u = bf(n, h, w, nf) if cp_rows else f32(n, h, w, nf)
+        new_u = (lambda: bf(n, h, w, nf)) if cp_rows else (lambda: f32(n, h, w, nf))
+        nblk = m.n_resgroups * m.n_resblocks
+        blocks, gtail_in = [], []  # keep: per RCAB (x_in, t, u, s, mean); per group the bf16 input of its tail conv
+        s_all = f32(nblk, n, nf) if keep else None
+        mean_all = f32(nblk, n, nf) if keep else None
         for g in range(m.n_resgroups):
             gin.copy_(xres)
             for b in range(m.n_resblocks):
                 pre = f"body.{g}.body.{b}.body"
+                mean = None
+                if keep:  # this RCAB's own t / u / s / mean, and its output shadow in a buffer of its own
+                    k = g * m.n_resblocks + b
+                    t, u, s, mean, xb_out = bf(n, h, w, nf), new_u(), s_all[k], mean_all[k], bf(n, h, w, nf)
+                    blocks.append((xb, t, u, s, mean))
+                else:
+                    xb_out = xb
                 P[f"{pre}.0"].fwd(xb, nf, 0, h, w, t, nf, 0, n, act=ACT_RELU)
                 ca = self.mods[f"{pre}.3"].conv_du
                 w1, b1, w2, b2 = ca[0].weight, ca[0].bias, ca[2].weight, ca[2].bias
                 if cp_rows:
                     P[f"{pre}.2"].fwd(t, nf, 0, h, w, u, nf, 0, n, ch_part=cpart)
-                    check(L.climsr_channel_attention_parts(ptr(cpart), n, cp_tpi, h * w, nf, ptr(w1), ptr(b1), ptr(w2), ptr(b2),
-                                                           w1.shape[0], ptr(self.ca_ws), ptr(s), st), f"channel attention {pre}")
+                    if keep:
+                        check(L.climsr_channel_attention_parts_keep(ptr(cpart), n, cp_tpi, h * w, nf, ptr(w1), ptr(b1), ptr(w2),
+                                                                    ptr(b2), w1.shape[0], ptr(self.ca_ws), ptr(s), ptr(mean), st),
+                              f"channel attention {pre}")
+                    else:
+                        check(L.climsr_channel_attention_parts(ptr(cpart), n, cp_tpi, h * w, nf, ptr(w1), ptr(b1), ptr(w2),
+                                                               ptr(b2), w1.shape[0], ptr(self.ca_ws), ptr(s), st),
+                              f"channel attention {pre}")
                 else:
                     P[f"{pre}.2"].fwd(t, nf, 0, h, w, u, nf, 0, n, out_mode=OUT_F32)
-                    check(L.climsr_channel_attention(ptr(u), n, h * w, nf, nf, ptr(w1), ptr(b1), ptr(w2), ptr(b2), w1.shape[0],
-                                                     ptr(self.ca_ws), ptr(s), st), f"channel attention {pre}")
-                check(L.climsr_ca_scale_add(ptr(u), int(bool(cp_rows)), nf, ptr(s), ptr(xres), ptr(xb), nf, n, h * w, nf, st),
+                    if keep:
+                        check(L.climsr_channel_attention_keep(ptr(u), n, h * w, nf, nf, ptr(w1), ptr(b1), ptr(w2), ptr(b2),
+                                                              w1.shape[0], ptr(self.ca_ws), ptr(s), ptr(mean), st),
+                              f"channel attention {pre}")
+                    else:
+                        check(L.climsr_channel_attention(ptr(u), n, h * w, nf, nf, ptr(w1), ptr(b1), ptr(w2), ptr(b2),
+                                                         w1.shape[0], ptr(self.ca_ws), ptr(s), st), f"channel attention {pre}")
+                check(L.climsr_ca_scale_add(ptr(u), int(bool(cp_rows)), nf, ptr(s), ptr(xres), ptr(xb_out), nf, n, h * w, nf, st),
                       f"rcab residual {pre}")
+                xb = xb_out
+            if keep:
+                gtail_in.append(xb)
+                xb_alt = bf(n, h, w, nf)
             # group tail conv + group skip (rcan.py:133-135), fp32 stream + bf16 shadow.  The shadow goes to the other
             # buffer of a pair: written in place, a tile's aux store would race the halo reads of its neighbours.
             P[f"body.{g}.body.{m.n_resblocks}"].fwd(xb, nf, 0, h, w, xres, nf, 0, n, res1=gin, res1_cs=nf, out_mode=OUT_F32,
@@ -230,26 +281,37 @@ class _RcanEngine:
         feat = bf(n, h, w, nf)
         P[f"body.{m.n_resgroups}"].fwd(xb, nf, 0, h, w, feat, nf, 0, n, res1=head, res1_cs=nf, out_mode=OUT_BF16)
         cur, ch, cw = feat, h, w
+        up_in = []
         for name, r in self.ups:
             c4 = P[name].cout
             t4 = bf(n, ch, cw, c4)
             P[name].fwd(cur, nf, 0, ch, cw, t4, c4, 0, n)
             nxt = bf(n, ch * r, cw * r, nf)
             check(L.climsr_pixel_shuffle_bf16(ptr(t4), n, ch, cw, nf, r, c4, ptr(nxt), nf, st), f"pixel shuffle {name}")
+            up_in.append(cur)
             cur, ch, cw = nxt, ch * r, cw * r
         assert (ch, cw) == (hh, ww)
-        return srcnn_tail(P, "tail.1", cur, nf, n, hh, ww, m.out_channels, elev, mask)
+        kept = {} if keep else None
+        out = srcnn_tail(P, "tail.1", cur, nf, n, hh, ww, m.out_channels, elev, mask, kept)
+        if not keep:
+            return out, None
+        # head output: only its gradient is needed (the global skip), which is the body conv's output gradient
+        kept.update(n=n, h=h, w=w, hh=hh, ww=ww, lr=lr, blocks=blocks, gtail_in=gtail_in, body_in=xb, up_in=up_in, up_out=cur,
+                    u_bf16=bool(cp_rows))
+        return out, kept
 
 
 def srcnn_tail(P: Dict[str, ConvPlan], last: str, feat: Tensor, feat_cs: int, n: int, hh: int, ww: int, oc: int, elev: Tensor,
-               mask: Tensor) -> Tensor:
+               mask: Tensor, kept: Optional[dict] = None) -> Tensor:
     """Last conv into channels [0, oc) of an 8-channel buffer, elev / mask after them (the torch.cat of rcan.py:190),
-    then SRCNN (srcnn.py:13-18) with fused ReLUs."""
+    then SRCNN (srcnn.py:13-18) with fused ReLUs.  ``kept`` (a dict) receives the 8-channel buffer as ``tail``."""
     dev = feat.device
     tail = torch.zeros((n, hh, ww, 8), dtype=torch.bfloat16, device=dev)
     P[last].fwd(feat, feat_cs, 0, hh, ww, tail, 8, 0, n)
     nchw_to_nhwc(elev.contiguous().float(), tail, 8, oc)
     nchw_to_nhwc(mask.contiguous().float(), tail, 8, oc + 1)
+    if kept is not None:
+        kept["tail"] = tail
     s1 = torch.empty((n, hh, ww, 64), dtype=torch.bfloat16, device=dev)
     P["srcnn.conv1"].fwd(tail, 8, 0, hh, ww, s1, 64, 0, n, act=ACT_RELU)
     s2 = torch.empty((n, hh, ww, 32), dtype=torch.bfloat16, device=dev)
@@ -262,3 +324,215 @@ def srcnn_tail(P: Dict[str, ConvPlan], last: str, feat: Tensor, feat_cs: int, n:
         P["srcnn.conv3"].fwd(s2, 32, 0, hh, ww, tmp, oc, 0, n, out_mode=OUT_F32)
         out.copy_(tmp.permute(0, 3, 1, 2))
     return out
+
+
+class _RcanTrainEngine(_RcanEngine):
+    """``_RcanEngine`` over a ``TrainableRCAN``'s flat parameters, with the backward."""
+
+    def _need_t(self, name: str) -> bool:
+        # no data gradient below the head; tail.1 (64 -> 1) and srcnn.conv2 / conv3 have kernels of their own
+        return name not in ("head.0", "tail.1", "srcnn.conv2", "srcnn.conv3")
+
+    def __init__(self, m: "TrainableRCAN"):
+        super().__init__(m)
+        self.srcnn_tail = SrcnnTail([self.plans[f"srcnn.conv{k}"] for k in (1, 2, 3)])
+        self.ws = Workspace()
+        self.scratch: Dict[str, Tensor] = {}
+        self.cab_ws = None
+
+    def _params_version(self):
+        # the fused AdamW writes the flat buffer through the C ABI and then calls repack_weights(); in-place torch
+        # writes (load_state_dict's copy_) bump the parameters' own counters
+        return self.m._flat._version, self.m._flat.data_ptr(), sum(p._version for p, _o, _n in self.m._flat_index)
+
+    def repack(self) -> None:
+        self.packer.run()
+        self.srcnn_tail.pack()
+        self.version = self._params_version()
+
+    def ensure_packed(self) -> None:
+        if self._params_version() != self.version:
+            self.repack()
+
+    def bind_grads(self) -> None:
+        for name, p in self.plans.items():
+            conv = self.mods[name]
+            p.gw, p.gb = conv.weight.grad, conv.bias.grad
+
+    def _scratch(self, key, shape, dtype, dev, zero=False):
+        t = self.scratch.get(key)
+        if t is None or tuple(t.shape) != tuple(shape) or t.device != dev:
+            t = torch.zeros(shape, dtype=dtype, device=dev) if zero else torch.empty(shape, dtype=dtype, device=dev)
+            self.scratch[key] = t
+        return t
+
+    def backward(self, gout: Tensor, sv: dict, accumulate: bool) -> None:
+        """Parameter gradients into the bound ``.grad`` views (= or += with ``accumulate``), the network walked in
+        reverse (rcan.py:181-192).  bf16 output gradients between convs, activation backward in the data-gradient
+        epilogues, fp32 only for the residual-stream gradient G."""
+        m, P, nf = self.m, self.plans, self.nf
+        n, h, w, hh, ww = sv["n"], sv["h"], sv["w"], sv["hh"], sv["ww"]
+        dev = gout.device
+        acc, ws = accumulate, self.ws
+        L = _lib.load()
+        st = _lib.stream_ptr()
+        npx = n * h * w
+        bf16, f32 = torch.bfloat16, torch.float32
+        gout = gout.contiguous().float()
+        # ---- SRCNN tail (srcnn.py:13-18): conv3 / conv2 gradients and conv1's output gradient in one launch that
+        # recomputes the two ReLU layers from the 8-channel buffer; dz8's channels 1..7 stay zero (elev / mask: no gradient)
+        dzA = self._scratch("dzA", (n, hh, ww, nf), bf16, dev)
+        dz8 = self._scratch("dz8", (n, hh, ww, 8), bf16, dev, zero=True)
+        self.srcnn_tail.bwd(sv["tail"], 8, 0, n, hh, ww, gout, dzA, ws, acc)
+        P["srcnn.conv1"].wgrad(sv["tail"], 8, 0, hh, ww, dzA, 64, n, ws, acc)
+        P["srcnn.conv1"].dgrad(dzA, 64, hh, ww, dz8, 8, 0, n, cout_t=1)
+        # ---- tail.1 (64 -> 1): its data gradient is the single-output stencil
+        P["tail.1"].wgrad(sv["up_out"], nf, 0, hh, ww, dz8, 8, n, ws, acc)
+        P["tail.1"].dgrad(dz8, 8, hh, ww, dzA, nf, 0, n)
+        # ---- Upsampler, last stage first: PixelShuffle backward (index map), then the 64 -> r*r*64 conv
+        gb = self._scratch("Gb", (n, h, w, nf), f32, dev)  # fp32 gradient at the body output (= at the head, global skip)
+        cur, ch, cw = dzA, hh, ww
+        for k in reversed(range(len(self.ups))):
+            name, r = self.ups[k]
+            c4 = P[name].cout
+            ch, cw = ch // r, cw // r
+            dz4 = self._scratch(f"dz4.{k}", (n, ch, cw, c4), bf16, dev)
+            _launch(f"pixel unshuffle {name}", lambda: L.climsr_pixel_unshuffle_bf16(ptr(cur), n, ch, cw, nf, r, nf, ptr(dz4), c4, st),
+                    nbytes=4 * n * ch * cw * c4)
+            P[name].wgrad(sv["up_in"][k], nf, 0, ch, cw, dz4, c4, n, ws, acc)
+            if k > 0:
+                nxt = self._scratch(f"dzup.{k}", (n, ch, cw, nf), bf16, dev)
+                P[name].dgrad(dz4, c4, ch, cw, nxt, nf, 0, n)
+                cur = nxt
+            else:
+                P[name].dgrad(dz4, c4, ch, cw, gb, nf, 0, n)
+        assert (ch, cw) == (h, w)
+        # ---- body conv + global skip (rcan.py:185-186): Gb stays for the head, G = conv^T(bf16(Gb)) enters the groups
+        dz64 = self._scratch("dz64", (n, h, w, nf), bf16, dev)
+        g_cur = self._scratch("G0", (n, h, w, nf), f32, dev)
+        g_alt = self._scratch("G1", (n, h, w, nf), f32, dev)
+        dzu = self._scratch("dzu", (n, h, w, nf), bf16, dev)
+        dzt = self._scratch("dzt", (n, h, w, nf), bf16, dev)
+        mbuf = self._scratch("m", (n, nf), f32, dev)
+        body = P[f"body.{m.n_resgroups}"]
+        act_grad(npx, nf, gb, nf, 0, None, 0, 0, ACT_NONE, dz64, nf)
+        body.wgrad(sv["body_in"], nf, 0, h, w, dz64, nf, n, ws, acc)
+        body.dgrad(dz64, nf, h, w, g_cur, nf, 0, n)
+        cr = m.n_feats // m.reduction
+        need = L.climsr_channel_attention_bwd_workspace(n, nf, cr)
+        if self.cab_ws is None or self.cab_ws.numel() * 8 < need or self.cab_ws.device != dev:
+            self.cab_ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
+        u_bf16 = int(sv["u_bf16"])
+        for g in reversed(range(m.n_resgroups)):
+            # group tail conv + group skip (rcan.py:133-135): g_cur = the gradient at the group's output, which is also
+            # the skip's gradient at the group's input; g_alt = conv^T(bf16(g_cur)) walks the RCABs
+            gt = P[f"body.{g}.body.{m.n_resblocks}"]
+            act_grad(npx, nf, g_cur, nf, 0, None, 0, 0, ACT_NONE, dz64, nf)
+            gt.wgrad(sv["gtail_in"][g], nf, 0, h, w, dz64, nf, n, ws, acc)
+            gt.dgrad(dz64, nf, h, w, g_alt, nf, 0, n)
+            for b in reversed(range(m.n_resblocks)):
+                pre = f"body.{g}.body.{b}.body"
+                x_in, t, u, s, mean = sv["blocks"][g * m.n_resblocks + b]
+                ca = self.mods[f"{pre}.3"].conv_du
+                c0, c2 = ca[0], ca[2]
+                # x_out = u s(u) + x_in: attention + scale backward (three launches) -> dzu = the gradient at u
+                _launch(f"channel attention bwd {pre}", lambda: L.climsr_channel_attention_bwd(
+                    ptr(g_alt), nf, ptr(u), u_bf16, nf, ptr(s), ptr(mean), n, h * w, nf, ptr(c0.weight), ptr(c0.bias), ptr(c2.weight),
+                    cr, ptr(self.cab_ws), ptr(mbuf), ptr(c0.weight.grad), ptr(c0.bias.grad), ptr(c2.weight.grad), ptr(c2.bias.grad),
+                    int(acc), ptr(dzu), nf, st), nbytes=npx * nf * (8 + 2 * u.element_size() + 2))
+                P[f"{pre}.2"].wgrad(t, nf, 0, h, w, dzu, nf, n, ws, acc)
+                P[f"{pre}.2"].dgrad(dzu, nf, h, w, dzt, nf, 0, n, act=ACT_RELU_BWD, res1=t, res1_cs=nf, res1_co=0)
+                P[f"{pre}.0"].wgrad(x_in, nf, 0, h, w, dzt, nf, n, ws, acc)
+                P[f"{pre}.0"].dgrad(dzt, nf, h, w, g_alt, nf, 0, n, accumulate=True)  # the RCAB skip passes G unchanged
+            axpby(npx, nf, 1.0, g_cur, nf, 0, 1.0, g_alt, nf, 0)  # + the group skip
+            g_cur, g_alt = g_alt, g_cur
+        # ---- head: the body path + the global skip; no data gradient below it
+        axpby(npx, nf, 1.0, gb, nf, 0, 1.0, g_cur, nf, 0)
+        act_grad(npx, nf, g_cur, nf, 0, None, 0, 0, ACT_NONE, dz64, nf)
+        P["head.0"].wgrad(sv["lr"], self.cin_pad, 0, h, w, dz64, nf, n, ws, acc)
+        hook = m._grad_ready_hook
+        if hook is not None:
+            hook(0)  # one bucket: the whole flat gradient buffer is final here
+
+
+class _RcanFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, elev, mask, engine_box, *params):
+        engine, keep, via_autograd = engine_box  # grad mode is off inside Function.forward: decided by the caller
+        out, saved = engine.run(x, elev, mask, keep=keep)
+        ctx.engine = engine
+        ctx.saved = saved
+        ctx.via_autograd = via_autograd
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        engine = ctx.engine
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            raise NotImplementedError("gradient w.r.t. the RCAN inputs is not implemented (never needed by the task)")
+        if ctx.saved is None:
+            raise RuntimeError("RCAN forward ran without saving activations")
+        net = engine.m
+        if ctx.via_autograd:  # torch DDP: the gradients go through AccumulateGrad (and the reducer's hooks)
+            buf, prev = net._begin_autograd_grads()
+            engine.bind_grads()
+            engine.backward(gout, ctx.saved, accumulate=False)
+            ctx.saved = None
+            return (None, None, None, None) + net._end_autograd_grads(buf, prev, ctx.needs_input_grad[4:])
+        acc = net.grads_as_views()
+        engine.bind_grads()
+        engine.backward(gout, ctx.saved, accumulate=acc)
+        ctx.saved = None
+        return (None, None, None, None) + tuple(None for _ in range(len(ctx.needs_input_grad) - 4))
+
+
+class TrainableRCAN(FlatParamsMixin, RCAN):
+    """``RCAN`` that trains (see the module docstring): same constructor, submodules, ``state_dict`` and forward."""
+
+    def __init__(self, n_resgroups: int = 10, n_resblocks: int = 20, n_feats: int = 64, reduction: int = 16,
+                 scaling_factor: int = 4, in_channels: int = 3, out_channels: int = 1, conv=default_conv, **kwargs):
+        if out_channels != 1:
+            raise NotImplementedError(f"TrainableRCAN: out_channels={out_channels}; the backward of the SRCNN tail is "
+                                      "single-output (RCAN runs inference for any)")
+        if n_feats != 64:
+            raise NotImplementedError(f"TrainableRCAN: n_feats={n_feats}; the backward is built for 64 features")
+        if not 1 <= in_channels <= 4:
+            raise NotImplementedError(f"TrainableRCAN: in_channels={in_channels}; the backward takes 1 to 4")
+        if scaling_factor not in (2, 4):
+            raise NotImplementedError(f"TrainableRCAN: scaling_factor={scaling_factor}; x2 and x4 train (the x3 upsampler's "
+                                      "64 -> 576 conv has no tested gradient route; RCAN runs x3 inference)")
+        if conv is not default_conv:
+            raise NotImplementedError("TrainableRCAN: a custom conv factory is not supported")
+        super().__init__(n_resgroups=n_resgroups, n_resblocks=n_resblocks, n_feats=n_feats, reduction=reduction,
+                         scaling_factor=scaling_factor, in_channels=in_channels, out_channels=out_channels, conv=conv, **kwargs)
+        self._flatten()
+        object.__setattr__(self, "_engine", None)
+        object.__setattr__(self, "_grad_ready_hook", None)
+
+    def set_grad_ready_hook(self, fn) -> None:
+        """Call ``fn(0)`` once at the end of every backward, when the whole flat gradient buffer is final (one bucket
+        for the overlapped DDP all-reduce, core/ddp.OverlappedGradAllReducer); ``fn=None`` removes it."""
+        object.__setattr__(self, "_grad_ready_hook", fn)
+
+    def _on_flat_moved(self):
+        object.__setattr__(self, "_engine", None)
+
+    def engine(self) -> _RcanTrainEngine:
+        self._ensure_flat()
+        eng = self._engine
+        if eng is None or eng.m is not self or eng.device != self._flat.device:
+            eng = _RcanTrainEngine(self)
+            object.__setattr__(self, "_engine", eng)
+        return eng
+
+    def repack_weights(self) -> None:
+        """Refresh the bf16 MFMA weight layouts after an in-place update of the fp32 master weights."""
+        self.engine().repack()
+
+    def forward(self, x: Tensor, elev: Tensor, mask: Tensor) -> Tensor:
+        if not x.is_cuda:
+            raise RuntimeError("TrainableRCAN runs in libclimsr_hip.so: inputs and parameters must be on a CUDA device")
+        eng = self.engine()
+        params = [p for p, _o, _n in self._flat_index]
+        keep = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        return _RcanFn.apply(x, elev, mask, (eng, keep, keep and self._route_grads_through_autograd()), *params)

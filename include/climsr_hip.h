@@ -479,6 +479,30 @@ int climsr_channel_attention(const float* u, int n, int64_t hw, int c, int u_cst
 int climsr_channel_attention_parts(const float* part, int n, int tiles_per_image, int64_t hw, int c, const float* w1,
                                    const float* b1, const float* w2, const float* b2, int cr, double* workspace, float* s,
                                    void* stream);
+/* The training forward's forms of the two calls above: the same launches, and mean[n][c] (fp32, required) receives the
+ * pooled mean the scale was computed from -- climsr_channel_attention_bwd recomputes the hidden layer from it. */
+int climsr_channel_attention_keep(const float* u, int n, int64_t hw, int c, int u_cstride, const float* w1, const float* b1,
+                                  const float* w2, const float* b2, int cr, double* workspace, float* s, float* mean,
+                                  void* stream);
+int climsr_channel_attention_parts_keep(const float* part, int n, int tiles_per_image, int64_t hw, int c, const float* w1,
+                                        const float* b1, const float* w2, const float* b2, int cr, double* workspace, float* s,
+                                        float* mean, void* stream);
+/* Backward of the RCAB's attention and residual, x_out = u * s(u) + x_in, given g = dL/dx_out (fp32 [n][hw][g_cstride]),
+ * u (fp32, or bf16 with u_bf16 = 1; [n][hw][u_cstride]) and the forward's s[n][c] and mean[n][c]:
+ *   q = sum_p g u;  dpre2 = q s (1 - s);  gw2 [c][cr] (+)= dpre2 (x) hid, gb2 [c] (+)= dpre2;  dhid = w2^T dpre2 where
+ *   hid > 0 (hid = relu(w1 mean + b1), the forward's formula);  gw1 [cr][c] (+)= dhid (x) mean, gb1 [cr] (+)= dhid;
+ *   m[n][c] = w1^T dhid / hw;  dzu = bf16(g s + m) ([n][hw][dzu_cstride]: the gradient at u).
+ * accumulate: 0 writes the four parameter gradients, 1 adds to them (gb1 / gb2 may be NULL).  dL/dx_in through the skip
+ * is g itself.  Three launches: per-slice partial sums of g u (fp32 per thread, fp64 across), one workgroup per image for
+ * the small layers (m and the image's factors), one pass that writes dzu and sums the images' factors in image order
+ * (fp64) into the parameter gradients.  No atomics: reruns are bit-identical.  c a multiple of 8 (<= 1024), cr <= c,
+ * g_cstride a multiple of 4, u_cstride of 4 (fp32) or 8 (bf16), dzu_cstride of 8; workspace =
+ * climsr_channel_attention_bwd_workspace(n, c, cr) bytes, 8-byte aligned. */
+size_t climsr_channel_attention_bwd_workspace(int n, int c, int cr);
+int climsr_channel_attention_bwd(const float* g, int g_cstride, const void* u, int u_bf16, int u_cstride, const float* s,
+                                 const float* mean, int n, int64_t hw, int c, const float* w1, const float* b1, const float* w2,
+                                 int cr, void* workspace, float* m, float* gw1, float* gb1, float* gw2, float* gb2,
+                                 int accumulate, uint16_t* dzu, int dzu_cstride, void* stream);
 /* RCAB residual with the attention scale (rcan.py:104-107): xres = u * s + xres (fp32 [n][hw][c]) and
  * xb = bf16(xres) ([n][hw][xb_cstride], the next conv's input); u = the RCAB body's output, fp32 or (u_bf16 = 1)
  * bf16, channel stride u_cstride.  c, strides multiples of 4. */
@@ -530,6 +554,11 @@ int64_t climsr_srcnn_packed_elems(void);
  * Bit-exact index map; c_out and out_cstride multiples of 8. */
 int climsr_pixel_shuffle_bf16(const uint16_t* x, int n, int h, int w, int c_out, int r, int in_cstride, uint16_t* y,
                               int out_cstride, void* stream);
+/* Its backward, the inverse index map (pixel unshuffle): x = the gradient at the shuffled map, bf16 [n][h*r][w*r]
+ * [in_cstride] (c_out channels), y[n][y][x][co*r*r+i*r+j] = x[n][y*r+i][x*r+j][co], bf16 [n][h][w][out_cstride].
+ * Bit-exact; c_out*r*r and out_cstride multiples of 8. */
+int climsr_pixel_unshuffle_bf16(const uint16_t* x, int n, int h, int w, int c_out, int r, int in_cstride, uint16_t* y,
+                                int out_cstride, void* stream);
 
 #ifdef __cplusplus
 }
