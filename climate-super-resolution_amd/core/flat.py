@@ -81,7 +81,7 @@ class FlatParamsMixin:
         self._rebind()
         self._on_flat_moved()
 
-    def _on_flat_moved(self) -> None:  # overridden by modules holding device plans
+    def _on_flat_moved(self) -> None:  # core/native.NativeModule drops its engine (the device plans) here
         pass
 
     def _apply(self, fn, recurse=True):  # keep the flat layout across .to()/.cuda()

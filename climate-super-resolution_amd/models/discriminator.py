@@ -12,33 +12,27 @@ where the flattened features are 8192 wide, i.e. 128x128 inputs with the default
   derivative (``climsr_bn_backward`` out_slope);
 * the two valid 3x3 convs (LeakyReLU 0.2 between them), the NCHW flatten, ``classification.0``
   (8192->100, MFMA split-K, rows padded to 128) and ``classification.1`` (100->1, no sigmoid).
-The ``avgpool`` member is constructed but unused, exactly as in the reference forward.
+The ``avgpool`` member is constructed but unused, exactly as in the reference forward.  Each call is one autograd
+node (the shared ``NativeFn`` of core/native.py); the flat gradient buffer is one grad-ready bucket.
 """
 from __future__ import annotations
 
-from typing import Dict, List
+from typing import List
 
 import torch
 import torch.nn as nn
 from torch import Tensor
 
 from .. import ops
-from ..core.flat import FlatParamsMixin
-from ..ops import ACT_LRELU, ACT_NONE, BatchedPacker, ConvPlan, Workspace
+from ..core.native import NativeEngine, NativeModule, bf16, f32
+from ..ops import ACT_LRELU, ACT_NONE, BatchedPacker, ConvPlan
 
 FC_PAD = 128  # classification.0 rows padded for the MFMA linear kernels (o % 64 == 0)
 
 
-def _bf16(shape, dev):
-    return torch.empty(shape, dtype=torch.bfloat16, device=dev)
-
-
-def _f32(shape, dev):
-    return torch.empty(shape, dtype=torch.float32, device=dev)
-
-
-class _PlainDEngine:
+class _PlainDEngine(NativeEngine):
     def __init__(self, d: "Discriminator"):
+        super().__init__(d)
         self.d = d
         dev = d.classification[0].weight.device
         feats = list(d.feature_extraction)
@@ -52,6 +46,7 @@ class _PlainDEngine:
             plan = ConvPlan(m.in_channels, m.out_channels, 3, m.stride[0], 0, f"feature_extraction.{i}")
             plan.bind(m.weight, m.bias, need_t=True)
             self.layers.append(dict(conv=m, plan=plan, rpad=rpad, slope=(act.negative_slope if act is not None else None), bn=bn))
+        self.bound = [(L["plan"], L["conv"]) for L in self.layers]
         self.packer = BatchedPacker([L["plan"] for L in self.layers], dev)
         fc0 = d.classification[0]
         self.feat = fc0.in_features
@@ -60,32 +55,18 @@ class _PlainDEngine:
         self.w0 = torch.zeros((FC_PAD, self.feat), dtype=torch.bfloat16, device=dev)
         self.b0 = torch.zeros((FC_PAD,), dtype=torch.float32, device=dev)
         self.w1 = torch.zeros((FC_PAD,), dtype=torch.float32, device=dev)
-        self.version = -1
-        self.ws = Workspace()
-        self.scratch: Dict[str, Tensor] = {}
 
-    def ensure_packed(self):
-        if self.d._flat._version != self.version:
-            self.repack()
-
-    def repack(self):
+    def pack(self):
         d = self.d
         self.packer.run()
         fc0, fc1 = d.classification[0], d.classification[1]
         ops.f32_to_bf16(fc0.weight, self.w0[: self.hid])
         self.b0[: self.hid].copy_(fc0.bias)
         self.w1[: self.hid].copy_(fc1.weight.view(-1))
-        self.version = d._flat._version
-
-    def _scr(self, key, shape, dtype, dev):
-        t = self.scratch.get(key)
-        if t is None or tuple(t.shape) != tuple(shape) or t.device != dev:
-            t = torch.zeros(shape, dtype=dtype, device=dev)
-            self.scratch[key] = t
-        return t
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x: Tensor, keep: bool, need_pt: bool):
+    def run(self, x: Tensor, keep: bool, need_w: bool):
+        """need_w: also write the transposed flattened features, which only classification.0's weight gradient reads."""
         d = self.d
         n, cin, h, w = x.shape
         dev = x.device
@@ -98,7 +79,7 @@ class _PlainDEngine:
         for L in self.layers:
             plan = L["plan"]
             if L["rpad"]:
-                xp = _bf16((n, hh + 2, ww + 2, cs), dev)
+                xp = bf16((n, hh + 2, ww + 2, cs), dev)
                 ops.reflect_pad1(a, n, hh, ww, cs, xp)
                 src, sh, sw = xp, hh + 2, ww + 2
             else:
@@ -108,7 +89,7 @@ class _PlainDEngine:
                 raise RuntimeError(f"Discriminator: {h}x{w} input leaves no pixels for {plan.name}; the reference architecture "
                                    f"only runs on inputs that flatten to 8192 (128x128), discriminator.py:42-46")
             c = plan.cout
-            t = _bf16((n, oh, ow, c), dev)
+            t = bf16((n, oh, ow, c), dev)
             slope = L["slope"]
             plan.fwd(src, cs, 0, sh, sw, t, c, 0, n, act=(ACT_LRELU if slope is not None else ACT_NONE),
                      slope=(slope if slope is not None else 0.0))
@@ -116,10 +97,10 @@ class _PlainDEngine:
             bn = L["bn"]
             out = t
             if bn is not None:
-                out = _bf16((n, oh, ow, c), dev)
+                out = bf16((n, oh, ow, c), dev)
                 npix = n * oh * ow
                 if d.training:
-                    mean, rstd = _f32((c,), dev), _f32((c,), dev)
+                    mean, rstd = f32((c,), dev), f32((c,), dev)
                     ops.bn_forward(t, npix, c, bn.weight, bn.bias, mean, rstd, out, ops.bn_workspace(npix, c, self.scratch, dev),
                                    bn.running_mean, bn.running_var, act=ACT_NONE, eps=bn.eps, momentum=bn.momentum,
                                    num_batches_tracked=bn.num_batches_tracked)
@@ -133,13 +114,13 @@ class _PlainDEngine:
             raise RuntimeError(f"Discriminator: flattened features {feat} != classification input {self.feat}; the reference "
                                f"architecture only runs on inputs that flatten to 8192 (128x128), discriminator.py:42-46")
         n_pad = (n + 31) // 32 * 32
-        p = _bf16((n, feat), dev)
-        p_t = torch.zeros((feat, n_pad), dtype=torch.bfloat16, device=dev) if need_pt else None
+        p = bf16((n, feat), dev)
+        p_t = torch.zeros((feat, n_pad), dtype=torch.bfloat16, device=dev) if need_w else None
         ops.adaptive_pool_fwd(a, n, hh, ww, cs, hh, ww, p, p_t, n_pad)  # identity pool = torch's NCHW flatten
-        hid = _f32((n, FC_PAD), dev)
-        lin_ws = self._scr("linws", (1024 * n * FC_PAD,), torch.float32, dev)
+        hid = f32((n, FC_PAD), dev)
+        lin_ws = self.buf("linws", (1024 * n * FC_PAD,), torch.float32, dev, zero=True)
         ops.linear_fwd(p, self.w0, self.b0, n, feat, FC_PAD, hid, lin_ws, act=ACT_NONE)
-        s = _f32((n, 1), dev)
+        s = f32((n, 1), dev)
         ops.d_head_fwd(hid, self.w1, d.classification[1].bias, n, FC_PAD, s, sigmoid=False)
         sv = None
         if keep:
@@ -154,15 +135,15 @@ class _PlainDEngine:
         fc0, fc1 = d.classification[0], d.classification[1]
         ds = ds.contiguous().float()
         acc = accumulate
-        du0 = _bf16((n, FC_PAD), dev)
+        du0 = bf16((n, FC_PAD), dev)
         du0_t = torch.zeros((FC_PAD, n_pad), dtype=torch.bfloat16, device=dev)
-        dw1 = self._scr("dw1", (FC_PAD,), torch.float32, dev).zero_()  # scratch: the head kernel's accumulate flag
-        db0 = self._scr("db0", (FC_PAD,), torch.float32, dev).zero_()  # must only affect the real bias gradient
+        dw1 = self.buf("dw1", (FC_PAD,), torch.float32, dev, zero=True).zero_()  # scratch: the head kernel's accumulate flag
+        db0 = self.buf("db0", (FC_PAD,), torch.float32, dev, zero=True).zero_()  # must only affect the real bias gradient
         db1 = fc1.bias.grad if need_w else None
         ops.d_head_bwd(sv["hid"], sv["s"], ds, self.w1, n, FC_PAD, n_pad, dw1 if need_w else None, db1, db0 if need_w else None,
                        acc, du0, du0_t, slope=1.0, sigmoid=False)
         if need_w:
-            dw0 = self._scr("dw0", (FC_PAD, feat), torch.float32, dev)
+            dw0 = self.buf("dw0", (FC_PAD, feat), torch.float32, dev, zero=True)
             ops.linear_wgrad(du0_t, sv["p_t"], n_pad, feat, FC_PAD, dw0, False)
             hd = self.hid
             if acc:
@@ -173,12 +154,12 @@ class _PlainDEngine:
                 fc0.weight.grad.copy_(dw0[:hd])
                 fc0.bias.grad.copy_(db0[:hd])
                 fc1.weight.grad.view(-1).copy_(dw1[:hd])
-        dp = self._scr("dp", (n, feat), torch.float32, dev)
+        dp = self.buf("dp", (n, feat), torch.float32, dev, zero=True)
         ops.linear_dgrad(du0, self.w0, n, feat, FC_PAD, dp)
         hh, ww, c = sv["hh"], sv["ww"], sv["c"]
-        da = _f32((n, hh, ww, c), dev)
+        da = f32((n, hh, ww, c), dev)
         ops.adaptive_pool_bwd(dp, n, hh, ww, c, hh, ww, da)
-        coef = self._scr("bncoef", (3 * 512,), torch.float32, dev)
+        coef = self.buf("bncoef", (3 * 512,), torch.float32, dev, zero=True)
         dx = None
         for li in reversed(range(len(self.layers))):
             L = self.layers[li]
@@ -187,7 +168,7 @@ class _PlainDEngine:
             oh, ow, c = R["oh"], R["ow"], plan.cout
             npix = n * oh * ow
             cz = (c + 7) // 8 * 8
-            dz = _bf16((n, oh, ow, cz), dev)
+            dz = bf16((n, oh, ow, cz), dev)
             if bn is not None:  # d(BN input) through the LeakyReLU that produced it
                 ops.bn_backward(da, R["t"], R["t"], npix, c, R["mean"], R["rstd"], bn.weight, ops.bn_workspace(npix, c, self.scratch, dev), coef,
                                 bn.weight.grad if need_w else None, bn.bias.grad if need_w else None, acc, dz, slope=1.0,
@@ -197,14 +178,12 @@ class _PlainDEngine:
             else:
                 ops.act_grad(npix, c, da, c, 0, None, 0, 0, ACT_NONE, dz, cz)
             if need_w:
-                plan.gw = conv.weight.grad
-                plan.gb = conv.bias.grad
                 plan.wgrad(R["src"], R["cs_in"], 0, R["sh"], R["sw"], dz, cz, n, self.ws, acc)
             if li > 0 or need_x:
-                gp = _f32((n, R["sh"], R["sw"], plan.cin), dev)
+                gp = f32((n, R["sh"], R["sw"], plan.cin), dev)
                 plan.dgrad(dz, cz, oh, ow, gp, plan.cin, 0, n)
                 if L["rpad"]:
-                    g = _f32((n, R["h_in"], R["w_in"], plan.cin), dev)
+                    g = f32((n, R["h_in"], R["w_in"], plan.cin), dev)
                     ops.reflect_pad1_bwd(gp, n, R["h_in"], R["w_in"], plan.cin, g)
                 else:
                     g = gp
@@ -212,37 +191,19 @@ class _PlainDEngine:
             if li == 0 and need_x:
                 dx = torch.empty((n, 1, sv["h"], sv["w"]), dtype=torch.float32, device=dev)
                 ops.nhwc_to_nchw(da, n, 1, sv["h"], sv["w"], plan.cin, 0, dx)
+        if need_w:
+            self.grads_final()
         return dx
 
 
-class _PlainDFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, box, *params):
-        engine, keep, need_pt, via_autograd = box
-        s, sv = engine.forward(x, keep, need_pt)
-        ctx.engine, ctx.sv, ctx.via_autograd = engine, sv, via_autograd
-        return s
-
-    @staticmethod
-    def backward(ctx, ds):
-        engine, sv = ctx.engine, ctx.sv
-        if sv is None:
-            raise RuntimeError("discriminator forward ran without saving activations")
-        need_w = any(ctx.needs_input_grad[2:])
-        need_x = ctx.needs_input_grad[0]
-        if need_w and ctx.via_autograd:  # torch DDP: the gradients go through AccumulateGrad (and the reducer's hooks)
-            buf, prev = engine.d._begin_autograd_grads()
-            dx = engine.backward(ds, sv, need_w, need_x, False)
-            ctx.sv = None
-            return (dx, None) + engine.d._end_autograd_grads(buf, prev, ctx.needs_input_grad[2:])
-        acc = engine.d.grads_as_views() if need_w else True
-        dx = engine.backward(ds, sv, need_w, need_x, acc)
-        ctx.sv = None
-        return (dx, None) + tuple(None for _ in range(len(ctx.needs_input_grad) - 2))
-
-
-class Discriminator(FlatParamsMixin, nn.Module):
+class Discriminator(NativeModule, nn.Module):
     """discriminator.py:5-46 (same members, keys and forward contract)."""
+
+    _engine_cls = _PlainDEngine
+    _input_grad = True
+    _label = "discriminator"
+    _gpu_only_msg = "climsr_amd.Discriminator runs on the GPU only (no CPU fallback)"
+    _engine_dies_on_apply = True  # buffers (BN running stats) may have moved too
 
     def __init__(self, in_channels=1, out_channels=64, num_conv_block=4):
         super().__init__()
@@ -259,31 +220,6 @@ class Discriminator(FlatParamsMixin, nn.Module):
         self.avgpool = nn.AdaptiveAvgPool2d((512, 512))
         self.classification = nn.Sequential(nn.Linear(8192, 100), nn.Linear(100, 1))
         self._flatten()
-        object.__setattr__(self, "_engine", None)
-
-    def _on_flat_moved(self):
-        object.__setattr__(self, "_engine", None)
-
-    def _apply(self, fn, recurse=True):
-        ret = super()._apply(fn, recurse)
-        object.__setattr__(self, "_engine", None)
-        return ret
-
-    def engine(self) -> _PlainDEngine:
-        self._ensure_flat()
-        if self._engine is None:
-            object.__setattr__(self, "_engine", _PlainDEngine(self))
-        return self._engine
-
-    def repack_weights(self) -> None:
-        self.engine().repack()
 
     def forward(self, x: Tensor) -> Tensor:
-        if not x.is_cuda:
-            raise RuntimeError("climsr_amd.Discriminator runs on the GPU only (no CPU fallback)")
-        eng = self.engine()
-        params = [p for p, _o, _n in self._flat_index]
-        grad_on = torch.is_grad_enabled()
-        need_w = grad_on and any(p.requires_grad for p in params)
-        keep = grad_on and (need_w or x.requires_grad)
-        return _PlainDFn.apply(x, (eng, keep, need_w, need_w and self._route_grads_through_autograd()), *params)
+        return self._native_forward(x)

@@ -16,11 +16,11 @@ Upsampler's ``nn.PixelShuffle`` as ``climsr_pixel_shuffle_bf16`` (bit-exact inde
 tail as in the ESRGAN generator.  ``RCAN`` is inference only: the reference runs it from ``inference.py`` with
 ``net.eval()``; calling it in training mode with gradients enabled raises (no silent non-training).
 
-``TrainableRCAN(FlatParamsMixin, RCAN)`` trains (``_target_: climsr_amd.models.rcan.TrainableRCAN`` with
+``TrainableRCAN(NativeModule, RCAN)`` trains (``_target_: climsr_amd.models.rcan.TrainableRCAN`` with
 ``generator_type: "rcan"``; the reference's rcan_pre_training / rcan_fine_tuning experiments): same constructor
 kwargs, submodule tree, ``state_dict`` keys, lenient ``load_state_dict`` and ``forward(x, elev, mask)``, so a checkpoint
-saved from one class loads into the other.  Its parameters live in one flat fp32 buffer (core/flat.py: the fused
-AdamW, both gradient routes, ``set_grad_ready_hook`` with one bucket).  Under ``no_grad`` its forward is the inference
+saved from one class loads into the other.  Its parameters live in one flat fp32 buffer (core/flat.py) and it runs as
+the shared autograd node of core/native.py (the fused AdamW, both gradient routes, the one-bucket grad-ready hook).  Under ``no_grad`` its forward is the inference
 path above, bit for bit; with gradients the same launches also keep what the backward reads (per RCAB the block input,
 the post-ReLU ``t``, ``u``, the attention scale and the pooled mean behind it).  The backward walks rcan.py:181-192 in
 reverse on the existing conv gradient calls plus ``climsr_channel_attention_bwd`` and ``climsr_pixel_unshuffle_bf16``
@@ -31,7 +31,7 @@ from __future__ import annotations
 
 import logging
 import math
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Tuple
 
 import torch
 import torch.nn as nn
@@ -39,10 +39,10 @@ from torch import Tensor
 
 from .. import _lib
 from .._lib import check, ptr
-from ..core.flat import FlatParamsMixin
-from ..ops import (ACT_NONE, ACT_RELU, ACT_RELU_BWD, OUT_BF16, OUT_F32, BatchedPacker, ConvPlan, SrcnnTail, Workspace, _launch, act_grad,
-                   axpby, nchw_to_nhwc)
-from .srcnn import SRCNNParams
+from ..core.native import NativeEngine, NativeModule
+from ..ops import (ACT_NONE, ACT_RELU, ACT_RELU_BWD, OUT_BF16, OUT_F32, BatchedPacker, ConvPlan, SrcnnTail, _launch, act_grad, axpby,
+                   nchw_to_nhwc)
+from .srcnn import SRCNNParams, srcnn_tail_bwd, srcnn_tail_fwd
 
 
 def default_conv(in_channels: int, out_channels: int, kernel_size: int, bias: bool = True) -> nn.Module:
@@ -291,82 +291,37 @@ class _RcanEngine:
             up_in.append(cur)
             cur, ch, cw = nxt, ch * r, cw * r
         assert (ch, cw) == (hh, ww)
-        kept = {} if keep else None
-        out = srcnn_tail(P, "tail.1", cur, nf, n, hh, ww, m.out_channels, elev, mask, kept)
+        out, tail, _s1, _s2 = srcnn_tail_fwd(P, "tail.1", cur, nf, n, hh, ww, m.out_channels, elev, mask)
         if not keep:
             return out, None
         # head output: only its gradient is needed (the global skip), which is the body conv's output gradient
-        kept.update(n=n, h=h, w=w, hh=hh, ww=ww, lr=lr, blocks=blocks, gtail_in=gtail_in, body_in=xb, up_in=up_in, up_out=cur,
-                    u_bf16=bool(cp_rows))
-        return out, kept
+        return out, dict(n=n, h=h, w=w, hh=hh, ww=ww, lr=lr, blocks=blocks, gtail_in=gtail_in, body_in=xb, up_in=up_in, up_out=cur,
+                         u_bf16=bool(cp_rows), tail=tail)
 
 
-def srcnn_tail(P: Dict[str, ConvPlan], last: str, feat: Tensor, feat_cs: int, n: int, hh: int, ww: int, oc: int, elev: Tensor,
-               mask: Tensor, kept: Optional[dict] = None) -> Tensor:
-    """Last conv into channels [0, oc) of an 8-channel buffer, elev / mask after them (the torch.cat of rcan.py:190),
-    then SRCNN (srcnn.py:13-18) with fused ReLUs.  ``kept`` (a dict) receives the 8-channel buffer as ``tail``."""
-    dev = feat.device
-    tail = torch.zeros((n, hh, ww, 8), dtype=torch.bfloat16, device=dev)
-    P[last].fwd(feat, feat_cs, 0, hh, ww, tail, 8, 0, n)
-    nchw_to_nhwc(elev.contiguous().float(), tail, 8, oc)
-    nchw_to_nhwc(mask.contiguous().float(), tail, 8, oc + 1)
-    if kept is not None:
-        kept["tail"] = tail
-    s1 = torch.empty((n, hh, ww, 64), dtype=torch.bfloat16, device=dev)
-    P["srcnn.conv1"].fwd(tail, 8, 0, hh, ww, s1, 64, 0, n, act=ACT_RELU)
-    s2 = torch.empty((n, hh, ww, 32), dtype=torch.bfloat16, device=dev)
-    P["srcnn.conv2"].fwd(s1, 64, 0, hh, ww, s2, 32, 0, n, act=ACT_RELU)
-    out = torch.empty((n, oc, hh, ww), dtype=torch.float32, device=dev)
-    if oc == 1:
-        P["srcnn.conv3"].fwd(s2, 32, 0, hh, ww, out, 1, 0, n, out_mode=OUT_F32)
-    else:
-        tmp = torch.empty((n, hh, ww, oc), dtype=torch.float32, device=dev)
-        P["srcnn.conv3"].fwd(s2, 32, 0, hh, ww, tmp, oc, 0, n, out_mode=OUT_F32)
-        out.copy_(tmp.permute(0, 3, 1, 2))
-    return out
-
-
-class _RcanTrainEngine(_RcanEngine):
-    """``_RcanEngine`` over a ``TrainableRCAN``'s flat parameters, with the backward."""
+class _RcanTrainEngine(NativeEngine, _RcanEngine):
+    """``_RcanEngine`` over a ``TrainableRCAN``'s flat parameters, with the backward (re-pack rule, scratch and
+    ``bind_grads`` from ``NativeEngine``)."""
 
     def _need_t(self, name: str) -> bool:
         # no data gradient below the head; tail.1 (64 -> 1) and srcnn.conv2 / conv3 have kernels of their own
         return name not in ("head.0", "tail.1", "srcnn.conv2", "srcnn.conv3")
 
     def __init__(self, m: "TrainableRCAN"):
-        super().__init__(m)
+        NativeEngine.__init__(self, m)
+        _RcanEngine.__init__(self, m)
+        self.bound = [(p, self.mods[name]) for name, p in self.plans.items()]
         self.srcnn_tail = SrcnnTail([self.plans[f"srcnn.conv{k}"] for k in (1, 2, 3)])
-        self.ws = Workspace()
-        self.scratch: Dict[str, Tensor] = {}
         self.cab_ws = None
 
-    def _params_version(self):
-        # the fused AdamW writes the flat buffer through the C ABI and then calls repack_weights(); in-place torch
-        # writes (load_state_dict's copy_) bump the parameters' own counters
-        return self.m._flat._version, self.m._flat.data_ptr(), sum(p._version for p, _o, _n in self.m._flat_index)
-
-    def repack(self) -> None:
+    def pack(self) -> None:
         self.packer.run()
         self.srcnn_tail.pack()
-        self.version = self._params_version()
 
-    def ensure_packed(self) -> None:
-        if self._params_version() != self.version:
-            self.repack()
+    def run(self, x: Tensor, elev: Tensor, mask: Tensor, keep: bool, need_w: bool = False):
+        return _RcanEngine.run(self, x, elev, mask, keep)
 
-    def bind_grads(self) -> None:
-        for name, p in self.plans.items():
-            conv = self.mods[name]
-            p.gw, p.gb = conv.weight.grad, conv.bias.grad
-
-    def _scratch(self, key, shape, dtype, dev, zero=False):
-        t = self.scratch.get(key)
-        if t is None or tuple(t.shape) != tuple(shape) or t.device != dev:
-            t = torch.zeros(shape, dtype=dtype, device=dev) if zero else torch.empty(shape, dtype=dtype, device=dev)
-            self.scratch[key] = t
-        return t
-
-    def backward(self, gout: Tensor, sv: dict, accumulate: bool) -> None:
+    def backward(self, gout: Tensor, sv: dict, need_w: bool, need_x: bool, accumulate: bool) -> None:
         """Parameter gradients into the bound ``.grad`` views (= or += with ``accumulate``), the network walked in
         reverse (rcan.py:181-192).  bf16 output gradients between convs, activation backward in the data-gradient
         epilogues, fp32 only for the residual-stream gradient G."""
@@ -381,39 +336,37 @@ class _RcanTrainEngine(_RcanEngine):
         gout = gout.contiguous().float()
         # ---- SRCNN tail (srcnn.py:13-18): conv3 / conv2 gradients and conv1's output gradient in one launch that
         # recomputes the two ReLU layers from the 8-channel buffer; dz8's channels 1..7 stay zero (elev / mask: no gradient)
-        dzA = self._scratch("dzA", (n, hh, ww, nf), bf16, dev)
-        dz8 = self._scratch("dz8", (n, hh, ww, 8), bf16, dev, zero=True)
-        self.srcnn_tail.bwd(sv["tail"], 8, 0, n, hh, ww, gout, dzA, ws, acc)
-        P["srcnn.conv1"].wgrad(sv["tail"], 8, 0, hh, ww, dzA, 64, n, ws, acc)
-        P["srcnn.conv1"].dgrad(dzA, 64, hh, ww, dz8, 8, 0, n, cout_t=1)
+        dzA = self.buf("dzA", (n, hh, ww, nf), bf16, dev)
+        dz8 = self.buf("dz8", (n, hh, ww, 8), bf16, dev, zero=True)
+        srcnn_tail_bwd(P, self.srcnn_tail, sv["tail"], n, hh, ww, gout, dzA, dz8, ws, acc)
         # ---- tail.1 (64 -> 1): its data gradient is the single-output stencil
         P["tail.1"].wgrad(sv["up_out"], nf, 0, hh, ww, dz8, 8, n, ws, acc)
         P["tail.1"].dgrad(dz8, 8, hh, ww, dzA, nf, 0, n)
         # ---- Upsampler, last stage first: PixelShuffle backward (index map), then the 64 -> r*r*64 conv
-        gb = self._scratch("Gb", (n, h, w, nf), f32, dev)  # fp32 gradient at the body output (= at the head, global skip)
+        gb = self.buf("Gb", (n, h, w, nf), f32, dev)  # fp32 gradient at the body output (= at the head, global skip)
         cur, ch, cw = dzA, hh, ww
         for k in reversed(range(len(self.ups))):
             name, r = self.ups[k]
             c4 = P[name].cout
             ch, cw = ch // r, cw // r
-            dz4 = self._scratch(f"dz4.{k}", (n, ch, cw, c4), bf16, dev)
+            dz4 = self.buf(f"dz4.{k}", (n, ch, cw, c4), bf16, dev)
             _launch(f"pixel unshuffle {name}", lambda: L.climsr_pixel_unshuffle_bf16(ptr(cur), n, ch, cw, nf, r, nf, ptr(dz4), c4, st),
                     nbytes=4 * n * ch * cw * c4)
             P[name].wgrad(sv["up_in"][k], nf, 0, ch, cw, dz4, c4, n, ws, acc)
             if k > 0:
-                nxt = self._scratch(f"dzup.{k}", (n, ch, cw, nf), bf16, dev)
+                nxt = self.buf(f"dzup.{k}", (n, ch, cw, nf), bf16, dev)
                 P[name].dgrad(dz4, c4, ch, cw, nxt, nf, 0, n)
                 cur = nxt
             else:
                 P[name].dgrad(dz4, c4, ch, cw, gb, nf, 0, n)
         assert (ch, cw) == (h, w)
         # ---- body conv + global skip (rcan.py:185-186): Gb stays for the head, G = conv^T(bf16(Gb)) enters the groups
-        dz64 = self._scratch("dz64", (n, h, w, nf), bf16, dev)
-        g_cur = self._scratch("G0", (n, h, w, nf), f32, dev)
-        g_alt = self._scratch("G1", (n, h, w, nf), f32, dev)
-        dzu = self._scratch("dzu", (n, h, w, nf), bf16, dev)
-        dzt = self._scratch("dzt", (n, h, w, nf), bf16, dev)
-        mbuf = self._scratch("m", (n, nf), f32, dev)
+        dz64 = self.buf("dz64", (n, h, w, nf), bf16, dev)
+        g_cur = self.buf("G0", (n, h, w, nf), f32, dev)
+        g_alt = self.buf("G1", (n, h, w, nf), f32, dev)
+        dzu = self.buf("dzu", (n, h, w, nf), bf16, dev)
+        dzt = self.buf("dzt", (n, h, w, nf), bf16, dev)
+        mbuf = self.buf("m", (n, nf), f32, dev)
         body = P[f"body.{m.n_resgroups}"]
         act_grad(npx, nf, gb, nf, 0, None, 0, 0, ACT_NONE, dz64, nf)
         body.wgrad(sv["body_in"], nf, 0, h, w, dz64, nf, n, ws, acc)
@@ -450,44 +403,15 @@ class _RcanTrainEngine(_RcanEngine):
         axpby(npx, nf, 1.0, gb, nf, 0, 1.0, g_cur, nf, 0)
         act_grad(npx, nf, g_cur, nf, 0, None, 0, 0, ACT_NONE, dz64, nf)
         P["head.0"].wgrad(sv["lr"], self.cin_pad, 0, h, w, dz64, nf, n, ws, acc)
-        hook = m._grad_ready_hook
-        if hook is not None:
-            hook(0)  # one bucket: the whole flat gradient buffer is final here
+        self.grads_final()
 
 
-class _RcanFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, elev, mask, engine_box, *params):
-        engine, keep, via_autograd = engine_box  # grad mode is off inside Function.forward: decided by the caller
-        out, saved = engine.run(x, elev, mask, keep=keep)
-        ctx.engine = engine
-        ctx.saved = saved
-        ctx.via_autograd = via_autograd
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        engine = ctx.engine
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            raise NotImplementedError("gradient w.r.t. the RCAN inputs is not implemented (never needed by the task)")
-        if ctx.saved is None:
-            raise RuntimeError("RCAN forward ran without saving activations")
-        net = engine.m
-        if ctx.via_autograd:  # torch DDP: the gradients go through AccumulateGrad (and the reducer's hooks)
-            buf, prev = net._begin_autograd_grads()
-            engine.bind_grads()
-            engine.backward(gout, ctx.saved, accumulate=False)
-            ctx.saved = None
-            return (None, None, None, None) + net._end_autograd_grads(buf, prev, ctx.needs_input_grad[4:])
-        acc = net.grads_as_views()
-        engine.bind_grads()
-        engine.backward(gout, ctx.saved, accumulate=acc)
-        ctx.saved = None
-        return (None, None, None, None) + tuple(None for _ in range(len(ctx.needs_input_grad) - 4))
-
-
-class TrainableRCAN(FlatParamsMixin, RCAN):
+class TrainableRCAN(NativeModule, RCAN):
     """``RCAN`` that trains (see the module docstring): same constructor, submodules, ``state_dict`` and forward."""
+
+    _engine_cls = _RcanTrainEngine
+    _label = "RCAN"
+    _gpu_only_msg = "TrainableRCAN runs in libclimsr_hip.so: inputs and parameters must be on a CUDA device"
 
     def __init__(self, n_resgroups: int = 10, n_resblocks: int = 20, n_feats: int = 64, reduction: int = 16,
                  scaling_factor: int = 4, in_channels: int = 3, out_channels: int = 1, conv=default_conv, **kwargs):
@@ -506,33 +430,6 @@ class TrainableRCAN(FlatParamsMixin, RCAN):
         super().__init__(n_resgroups=n_resgroups, n_resblocks=n_resblocks, n_feats=n_feats, reduction=reduction,
                          scaling_factor=scaling_factor, in_channels=in_channels, out_channels=out_channels, conv=conv, **kwargs)
         self._flatten()
-        object.__setattr__(self, "_engine", None)
-        object.__setattr__(self, "_grad_ready_hook", None)
-
-    def set_grad_ready_hook(self, fn) -> None:
-        """Call ``fn(0)`` once at the end of every backward, when the whole flat gradient buffer is final (one bucket
-        for the overlapped DDP all-reduce, core/ddp.OverlappedGradAllReducer); ``fn=None`` removes it."""
-        object.__setattr__(self, "_grad_ready_hook", fn)
-
-    def _on_flat_moved(self):
-        object.__setattr__(self, "_engine", None)
-
-    def engine(self) -> _RcanTrainEngine:
-        self._ensure_flat()
-        eng = self._engine
-        if eng is None or eng.m is not self or eng.device != self._flat.device:
-            eng = _RcanTrainEngine(self)
-            object.__setattr__(self, "_engine", eng)
-        return eng
-
-    def repack_weights(self) -> None:
-        """Refresh the bf16 MFMA weight layouts after an in-place update of the fp32 master weights."""
-        self.engine().repack()
 
     def forward(self, x: Tensor, elev: Tensor, mask: Tensor) -> Tensor:
-        if not x.is_cuda:
-            raise RuntimeError("TrainableRCAN runs in libclimsr_hip.so: inputs and parameters must be on a CUDA device")
-        eng = self.engine()
-        params = [p for p, _o, _n in self._flat_index]
-        keep = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        return _RcanFn.apply(x, elev, mask, (eng, keep, keep and self._route_grads_through_autograd()), *params)
+        return self._native_forward(x, elev, mask)

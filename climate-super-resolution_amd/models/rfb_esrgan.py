@@ -7,36 +7,27 @@ arithmetic runs in libclimsr_hip: implicit-GEMM convs (stride 1/2; the stride-2 
 stride-1 conv over the zero-inserted gradient), BatchNorm fused with LeakyReLU(0.2), the adaptive
 16->14 average pool, fc.0 (100352->1024) on MFMA with split-K, and the LeakyReLU/fc.2/Sigmoid head.
 
-Each call is one autograd node.  Weight/BN-affine gradients land in one flat fp32 buffer and are
+Each call is one autograd node (the shared ``NativeFn`` of core/native.py).  Weight/BN-affine gradients land in one flat fp32 buffer and are
 only computed when the parameters require grad (Lightning toggles D off during the generator
 update, pl_gan.py:63-79); the input gradient (into the generator) is computed when the input
 requires grad.
 """
 from __future__ import annotations
 
-from typing import Dict, List
-
 import torch
 import torch.nn as nn
 from torch import Tensor
 
 from .. import ops
-from ..core.flat import FlatParamsMixin
-from ..ops import ACT_LRELU, ACT_LRELU_BWD, BatchedPacker, ConvPlan, Workspace
+from ..core.native import NativeEngine, NativeModule, bf16, f32, pack_input8
+from ..ops import ACT_LRELU, ACT_LRELU_BWD, BatchedPacker, ConvPlan
 
 POOL = 14
 
 
-def _bf16(shape, dev):
-    return torch.empty(shape, dtype=torch.bfloat16, device=dev)
-
-
-def _f32(shape, dev):
-    return torch.empty(shape, dtype=torch.float32, device=dev)
-
-
-class _DEngine:
+class _DEngine(NativeEngine):
     def __init__(self, d: "RFBESRGANDiscriminator"):
+        super().__init__(d)
         self.d = d
         dev = d.fc[0].weight.device
         self.layers = []  # (conv module, bn module or None, ConvPlan)
@@ -47,65 +38,44 @@ class _DEngine:
                 plan = ConvPlan(m.in_channels, m.out_channels, 3, m.stride[0], 1, f"features.{i}")
                 plan.bind(m.weight, None, need_t=True)
                 self.layers.append((m, bn, plan))
+        self.bound = [(p, c) for c, _b, p in self.layers]
         self.packer = BatchedPacker([p for _c, _b, p in self.layers], dev)
         self.fc0_bf16 = torch.empty(d.fc[0].weight.shape, dtype=torch.bfloat16, device=dev)
-        self.version = -1
-        self.ws = Workspace()
-        self.scratch: Dict[str, Tensor] = {}
 
-    def ensure_packed(self):
-        v = self.d._flat._version
-        if v != self.version:
-            self.repack()
-
-    def repack(self, mirror_done: bool = False):
+    def pack(self, mirror_done: bool = False):
         """mirror_done: the optimizer's AdamW pass already wrote fc0_bf16 (climsr_adamw_step_mirror)."""
         self.packer.run()
         if not mirror_done:
             ops.f32_to_bf16(self.d.fc[0].weight, self.fc0_bf16)
-        self.version = self.d._flat._version
-
-    def _scr(self, key, shape, dtype, dev):
-        t = self.scratch.get(key)
-        if t is None or tuple(t.shape) != tuple(shape) or t.device != dev:
-            t = torch.empty(shape, dtype=dtype, device=dev)
-            self.scratch[key] = t
-        return t
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x: Tensor, keep: bool, need_pt: bool):
+    def run(self, x: Tensor, keep: bool, need_w: bool):
+        """need_w: also write the transposed pooled features, which only fc.0's weight gradient reads."""
         d = self.d
         n, cin, h, w = x.shape
         dev = x.device
         self.ensure_packed()
         cpad = (cin + 7) // 8 * 8
-        xc = x.contiguous().float()
-        if cpad == 8:  # channels 0..cin-1 + zero padding in one full-pixel pass
-            x8 = torch.empty((n, h, w, 8), dtype=torch.bfloat16, device=dev)
-            ops.pack_planes8([(xc, k) for k in range(cin)], n, h, w, x8)
-        else:
-            x8 = torch.zeros((n, h, w, cpad), dtype=torch.bfloat16, device=dev)
-            ops.nchw_to_nhwc(xc, x8, cpad, 0)
-        a_prev, cs_prev, hh, ww = x8, cpad, h, w
+        a_prev, cs_prev, hh, ww = pack_input8(x, cpad), cpad, h, w
         saved = []
         training = d.training
         for conv, bn, plan in self.layers:
             oh, ow = plan.out_hw(hh, ww)
             c = plan.cout
             if bn is None:
-                a = _bf16((n, oh, ow, c), dev)
+                a = bf16((n, oh, ow, c), dev)
                 plan.fwd(a_prev, cs_prev, 0, hh, ww, a, c, 0, n, act=ACT_LRELU, use_bias=False)
                 saved.append(dict(a_in=a_prev, cs_in=cs_prev, h_in=hh, w_in=ww, z=None, a=a, mean=None, rstd=None, oh=oh, ow=ow))
             else:
-                z = _bf16((n, oh, ow, c), dev)
-                a = _bf16((n, oh, ow, c), dev)
+                z = bf16((n, oh, ow, c), dev)
+                a = bf16((n, oh, ow, c), dev)
                 npix = n * oh * ow
                 # train mode: the conv epilogue emits the batch statistics' partial sums (no pass over z for them)
                 nparts = plan.bn_parts(cs_prev, hh, ww, n, c) if training else 0
-                part = self._scr(f"bnpart{len(saved)}", (max(nparts, 1) * 2 * c,), torch.float64, dev) if nparts else None
+                part = self.buf(f"bnpart{len(saved)}", (max(nparts, 1) * 2 * c,), torch.float64, dev) if nparts else None
                 plan.fwd(a_prev, cs_prev, 0, hh, ww, z, c, 0, n, use_bias=False, bn_part=part)
                 if training:
-                    mean, rstd = _f32((c,), dev), _f32((c,), dev)
+                    mean, rstd = f32((c,), dev), f32((c,), dev)
                     if nparts:
                         ops.bn_forward_parts(part, nparts, z, npix, c, bn.weight, bn.bias, mean, rstd, a, bn.running_mean,
                                              bn.running_var, eps=bn.eps, momentum=bn.momentum,
@@ -122,15 +92,15 @@ class _DEngine:
         c = cs_prev
         feat = c * POOL * POOL
         n_pad = (n + 31) // 32 * 32
-        p = _bf16((n, feat), dev)
-        p_t = torch.zeros((feat, n_pad), dtype=torch.bfloat16, device=dev) if need_pt else None
+        p = bf16((n, feat), dev)
+        p_t = torch.zeros((feat, n_pad), dtype=torch.bfloat16, device=dev) if need_w else None
         ops.adaptive_pool_fwd(a_prev, n, hh, ww, c, POOL, POOL, p, p_t, n_pad)
         fc0, fc2 = d.fc[0], d.fc[2]
-        hid = _f32((n, fc0.out_features), dev)
+        hid = f32((n, fc0.out_features), dev)
         nsplit_max = 3072 // ((fc0.out_features + 63) // 64) + 1
-        lin_ws = self._scr("linws", (nsplit_max * n * fc0.out_features,), torch.float32, dev)
+        lin_ws = self.buf("linws", (nsplit_max * n * fc0.out_features,), torch.float32, dev)
         ops.linear_fwd(p, self.fc0_bf16, fc0.bias, n, feat, fc0.out_features, hid, lin_ws, act=ACT_LRELU, slope=0.2)
-        s = _f32((n, 1), dev)
+        s = f32((n, 1), dev)
         ops.d_head_fwd(hid, fc2.weight, fc2.bias, n, fc0.out_features, s)
         sv = None
         if keep:
@@ -145,7 +115,7 @@ class _DEngine:
         fc0, fc2 = d.fc[0], d.fc[2]
         o = fc0.out_features
         ds = ds.contiguous().float()
-        du0 = _bf16((n, o), dev)
+        du0 = bf16((n, o), dev)
         du0_t = torch.zeros((o, n_pad), dtype=torch.bfloat16, device=dev)
         acc = accumulate
         ops.d_head_bwd(sv["hid"], sv["s"], ds, fc2.weight, n, o, n_pad, fc2.weight.grad if need_w else None,
@@ -159,12 +129,12 @@ class _DEngine:
                 if d._ready_calls >= d._ready_need:
                     object.__setattr__(d, "_ready_calls", 0)
                     hook(d._fc_flat_lo())
-        dp = self._scr("dp", (n, feat), torch.float32, dev)
+        dp = self.buf("dp", (n, feat), torch.float32, dev)
         ops.linear_dgrad(du0, self.fc0_bf16, n, feat, o, dp)
         hh, ww, c = sv["hh"], sv["ww"], sv["c"]
-        da = _f32((n, hh, ww, c), dev)
+        da = f32((n, hh, ww, c), dev)
         ops.adaptive_pool_bwd(dp, n, hh, ww, c, POOL, POOL, da)
-        coef = self._scr("bncoef", (3 * 512,), torch.float32, dev)
+        coef = self.buf("bncoef", (3 * 512,), torch.float32, dev)
         dx = None
         dz_next = None  # layer 0's output gradient, written directly by layer 1's data gradient
         fused = {}  # layer -> (part, nparts): its BN backward statistics, from the next layer's data-gradient epilogue
@@ -177,7 +147,7 @@ class _DEngine:
             if bn is not None:
                 # lrelu'(a) recomputed from z: the activation is not read; da is the bf16 data gradient of the
                 # next conv (fp32 only for the last layer, from the pooling backward)
-                dz = _bf16((n, oh, ow, cz), dev)
+                dz = bf16((n, oh, ow, cz), dev)
                 if li in fused:
                     part, nparts = fused.pop(li)
                     ops.bn_backward_parts(part, nparts, da, L["z"], npix, c, L["mean"], L["rstd"], bn.weight, bn.bias, coef,
@@ -189,11 +159,9 @@ class _DEngine:
             elif dz_next is not None:
                 dz = dz_next
             else:
-                dz = _bf16((n, oh, ow, cz), dev)
+                dz = bf16((n, oh, ow, cz), dev)
                 ops.act_grad(npix, c, da, c, 0, L["a"], c, 0, ACT_LRELU, dz, cz)
             if need_w:
-                plan.gw = conv.weight.grad
-                plan.gb = None
                 plan.wgrad(L["a_in"], L["cs_in"], 0, L["h_in"], L["w_in"], dz, cz, n, self.ws, acc)
             if li > 0 or need_x:
                 prev_bn = self.layers[li - 1][1] if li > 0 else None
@@ -201,24 +169,24 @@ class _DEngine:
                     # the previous layer has no BN (layer 0): its LeakyReLU' (from its stored bf16 activation) goes
                     # into this data gradient's epilogue, which writes that layer's bf16 output gradient
                     P0 = sv["layers"][li - 1]
-                    g = _bf16((n, L["h_in"], L["w_in"], plan.cin), dev)
+                    g = bf16((n, L["h_in"], L["w_in"], plan.cin), dev)
                     plan.dgrad(dz, cz, oh, ow, g, plan.cin, 0, n, act=ACT_LRELU_BWD, res1=P0["a"], res1_cs=plan.cin, res1_co=0)
                     dz_next = g
                 elif li > 0:
-                    g = _bf16((n, L["h_in"], L["w_in"], plan.cin), dev)  # bf16: read by the previous layer's BN backward
+                    g = bf16((n, L["h_in"], L["w_in"], plan.cin), dev)  # bf16: read by the previous layer's BN backward
                     P = sv["layers"][li - 1]
                     # that BN's backward statistics (sum d, sum d * xhat) come from this data gradient's epilogue
                     # where its kernel supports them: the separate statistics pass over g and z is skipped
                     nparts = plan.dgrad_bn_parts(cz, oh, ow, plan.cin, n, plan.cin) if P["mean"] is not None else 0
                     if nparts:
-                        part = self._scr(f"bnbwd{li - 1}", (nparts * 2 * plan.cin,), torch.float64, dev)
+                        part = self.buf(f"bnbwd{li - 1}", (nparts * 2 * plan.cin,), torch.float64, dev)
                         plan.dgrad(dz, cz, oh, ow, g, plan.cin, 0, n,
                                    bn_bwd=(part, P["z"], plan.cin, P["mean"], P["rstd"], prev_bn.weight, prev_bn.bias))
                         fused[li - 1] = (part, nparts)
                     else:
                         plan.dgrad(dz, cz, oh, ow, g, plan.cin, 0, n)
                 else:
-                    g = _f32((n, L["h_in"], L["w_in"], plan.cin), dev)
+                    g = f32((n, L["h_in"], L["w_in"], plan.cin), dev)
                     plan.dgrad(dz, cz, oh, ow, g, plan.cin, 0, n)
                 da = g
             if li == 0 and need_x:
@@ -227,34 +195,14 @@ class _DEngine:
         return dx
 
 
-class _DFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, box, *params):
-        engine, keep, need_pt, via_autograd = box
-        s, sv = engine.forward(x, keep, need_pt)
-        ctx.engine, ctx.sv, ctx.via_autograd = engine, sv, via_autograd
-        return s
-
-    @staticmethod
-    def backward(ctx, ds):
-        engine, sv = ctx.engine, ctx.sv
-        if sv is None:
-            raise RuntimeError("discriminator forward ran without saving activations")
-        need_w = any(ctx.needs_input_grad[2:])
-        need_x = ctx.needs_input_grad[0]
-        if need_w and ctx.via_autograd:  # torch DDP: the gradients go through AccumulateGrad (and the reducer's hooks)
-            buf, prev = engine.d._begin_autograd_grads()
-            dx = engine.backward(ds, sv, need_w, need_x, False)
-            ctx.sv = None
-            return (dx, None) + engine.d._end_autograd_grads(buf, prev, ctx.needs_input_grad[2:])
-        acc = engine.d.grads_as_views() if need_w else True
-        dx = engine.backward(ds, sv, need_w, need_x, acc)
-        ctx.sv = None
-        return (dx, None) + tuple(None for _ in range(len(ctx.needs_input_grad) - 2))
-
-
-class RFBESRGANDiscriminator(FlatParamsMixin, nn.Module):
+class RFBESRGANDiscriminator(NativeModule, nn.Module):
     r"""The main architecture of the discriminator. Similar to VGG structure (rfb_esrgan.py:23-69)."""
+
+    _engine_cls = _DEngine
+    _input_grad = True
+    _label = "discriminator"
+    _gpu_only_msg = "climsr_amd.RFBESRGANDiscriminator runs on the GPU only (no CPU fallback)"
+    _engine_dies_on_apply = True  # buffers (BN running stats) may have moved too
 
     def __init__(self, in_channels=1):
         super().__init__()
@@ -291,8 +239,6 @@ class RFBESRGANDiscriminator(FlatParamsMixin, nn.Module):
             nn.Sigmoid(),
         )
         self._flatten()
-        object.__setattr__(self, "_engine", None)
-        object.__setattr__(self, "_grad_ready_hook", None)
         object.__setattr__(self, "_ready_calls", 0)
         object.__setattr__(self, "_ready_need", 1)
 
@@ -317,29 +263,5 @@ class RFBESRGANDiscriminator(FlatParamsMixin, nn.Module):
                 return off
         raise KeyError("fc.0.weight not in the flat parameter index")
 
-    def _on_flat_moved(self):
-        object.__setattr__(self, "_engine", None)
-
-    def _apply(self, fn, recurse=True):
-        ret = super()._apply(fn, recurse)
-        object.__setattr__(self, "_engine", None)  # buffers (BN running stats) may have moved too
-        return ret
-
-    def engine(self) -> _DEngine:
-        self._ensure_flat()
-        if self._engine is None:
-            object.__setattr__(self, "_engine", _DEngine(self))
-        return self._engine
-
-    def repack_weights(self, mirror_done: bool = False) -> None:
-        self.engine().repack(mirror_done=mirror_done)
-
     def forward(self, input: Tensor) -> Tensor:
-        if not input.is_cuda:
-            raise RuntimeError("climsr_amd.RFBESRGANDiscriminator runs on the GPU only (no CPU fallback)")
-        eng = self.engine()
-        params = [p for p, _o, _n in self._flat_index]
-        grad_on = torch.is_grad_enabled()
-        need_w = grad_on and any(p.requires_grad for p in params)
-        keep = grad_on and (need_w or input.requires_grad)
-        return _DFn.apply(input, (eng, keep, need_w, need_w and self._route_grads_through_autograd()), *params)
+        return self._native_forward(input)
