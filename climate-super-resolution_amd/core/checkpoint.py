@@ -69,6 +69,25 @@ def load_checkpoint(path: str, map_location="cpu", trusted: bool = False) -> Dic
         return torch.load(path, map_location=map_location, weights_only=False)
 
 
+def restore_training_state(module: nn.Module, path: str, optimizers: Iterable[torch.optim.Optimizer] = (),
+                           schedulers: Iterable[Any] = (), trusted: bool = False):
+    """Lightning's ``resume_from_checkpoint`` (cli/train.py:91-93): weights, every optimizer's and scheduler's state.
+    Returns the file's ``(epoch, global_step)``.  Optimizer states are read on the CPU and moved by each optimizer's
+    ``load_state_dict`` (the fused AdamW checks its moment buffers against the flat parameter buffer there)."""
+    ckpt = load_checkpoint(path, map_location="cpu", trusted=trusted)
+    optimizers, schedulers = list(optimizers), [s["scheduler"] if isinstance(s, dict) else s for s in schedulers]
+    ostates, sstates = ckpt.get("optimizer_states") or [], ckpt.get("lr_schedulers") or []
+    if len(ostates) != len(optimizers) or len(sstates) != len(schedulers):
+        raise ValueError(f"{path}: holds {len(ostates)} optimizer and {len(sstates)} scheduler states, the trainer has "
+                         f"{len(optimizers)} and {len(schedulers)}")
+    module.load_state_dict(ckpt["state_dict"], strict=True)
+    for opt, st in zip(optimizers, ostates):
+        opt.load_state_dict(st)
+    for sch, st in zip(schedulers, sstates):
+        sch.load_state_dict(st)
+    return int(ckpt["epoch"]), int(ckpt["global_step"])
+
+
 def strip_prefix(state_dict: Dict[str, torch.Tensor], prefix: str) -> Dict[str, torch.Tensor]:
     return {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
 

@@ -158,6 +158,30 @@ class AdamW(torch.optim.Optimizer):
         self.owner = owner
         self._hp = None
 
+    def load_state_dict(self, state_dict) -> None:
+        """``torch.optim.Optimizer.load_state_dict`` copies the flat update's state (string keys ``"group%d"``: step, m,
+        v) as it is, on whatever device the file was read to -- and the kernel takes raw pointers.  So every group's m
+        and v are checked against the group's flat parameter buffer (shape, dtype, contiguity: ``ValueError``) and moved
+        to its device here, before any step."""
+        super().load_state_dict(state_dict)
+        for gi, group in enumerate(self.param_groups):
+            st = self.state.get("group%d" % gi)
+            if not st or ("m" not in st and "v" not in st):
+                continue
+            flat = _flat_owner(group["params"])
+            if flat is None:
+                raise ValueError(f"AdamW.load_state_dict: group {gi} carries flat-buffer moments but its parameters are "
+                                 "not the views of one flat buffer")
+            if not isinstance(st.get("step"), int) or st["step"] < 1:
+                raise ValueError(f"AdamW.load_state_dict: group {gi} has moments but step={st.get('step')!r}")
+            for k in ("m", "v"):
+                t = st.get(k)
+                if not isinstance(t, torch.Tensor) or t.shape != flat.shape or t.dtype != flat.dtype or not t.is_contiguous():
+                    got = f"{tuple(t.shape)} {t.dtype} contiguous={t.is_contiguous()}" if isinstance(t, torch.Tensor) else repr(t)
+                    raise ValueError(f"AdamW.load_state_dict: group {gi} moment {k!r} is {got}; the flat parameter buffer "
+                                     f"is {tuple(flat.shape)} {flat.dtype}")
+                st[k] = t.to(flat.device, copy=True)  # never the caller's tensor: the update writes it in place
+
     def _hparams(self, group, step: int, device) -> torch.Tensor:
         """The kernel's scalars {lr, beta1, beta2, eps, wd, lr / bc1, sqrt(bc2), 0} for this group's ``step``-th update."""
         lr = group["lr"]

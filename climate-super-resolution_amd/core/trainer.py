@@ -22,12 +22,155 @@ default trainer launches exactly what is described above:
   about to step, before clipping, as device tensors (no rounding to 4 decimals, no stale norms of the other network).
 - ``terminate_on_nan``: reads the loss and the norm's finite flag before each optimizer step (the only host sync these
   options introduce) and raises ``ValueError`` instead of stepping.
+
+Epochs, validation, test and resume (all off by default; ``fit(batches)`` stays the single pass described above, with
+``max_epochs`` ignored):
+
+- ``fit(datamodule=dm)`` (or ``Trainer(datamodule=dm)`` and ``fit()``): ``dm.train_dataloader()`` / ``dm.val_dataloader()``
+  are called once and iterated once per epoch, for ``max_epochs`` epochs or until ``max_steps`` optimizer steps (the
+  epoch is cut there and not validated).  ``limit_train_batches`` (int count / float fraction) bounds each epoch.
+  ``current_epoch`` and ``global_step`` (optimizer steps of optimizer 0) live on the trainer and the module.
+- ``validate``: after epoch e when (e + 1) % ``check_val_every_n_epoch`` == 0, or on its own.  eval() + no_grad, then
+  back to train(); ``validation_step`` per batch, ``validation_epoch_end(outputs)`` at the end.  Every scalar tensor of
+  the step's dict becomes an epoch value: the mean over batches weighted by ``batch["lr"].shape[0]`` (Lightning 1.x's
+  ``on_epoch=True`` reduction), accumulated on the device in fp64 with no host read.  They land, with ``hp_metric``, in
+  ``trainer.callback_metrics`` and ``module.logged``.  ``limit_val_batches``; ``num_sanity_val_steps`` (default 0 here).
+- ``test(per_image=, baselines=)``: the same loop over ``test_step``; returns Lightning's ``[{name: float}]``.  With
+  ``per_image`` the ``SRMetrics.per_image`` rows of every batch's ``sr`` are concatenated in loader order as
+  ``trainer.test_table`` ([N, 17] float64 on the device); ``baselines`` adds ``test_table_nearest`` / ``test_table_cubic``.
+- ``callbacks=[ModelCheckpoint(...), EarlyStopping(...)]`` run after each validation inside ``fit`` (one host read of the
+  monitored value each).  ``resume_from_checkpoint=path`` restores weights, optimizer and scheduler states, ``epoch`` and
+  ``global_step`` and continues with the next epoch, bit-identical to the uninterrupted run.
 """
 from __future__ import annotations
 
+import itertools
+import math
+import os
+import re
 from typing import Any, Dict, Iterable, List, Optional
 
 NET_NAMES = ("generator", "discriminator")
+_END = object()
+
+
+class ListDataModule:
+    """A datamodule over lists (or any re-iterable) of ready batches."""
+
+    def __init__(self, train, val=None, test=None):
+        self.train_dataloader, self.val_dataloader, self.test_dataloader = (lambda: train), (lambda: val), (lambda: test)
+
+
+def _limited(batches, limit, what: str):
+    """``batches`` cut to Lightning's ``limit_*_batches``: an int is a batch count, a float a fraction of ``len()``."""
+    if isinstance(limit, bool) or not isinstance(limit, (int, float)) or limit < 0:
+        raise ValueError(f"{what} must be an int count or a float fraction >= 0, got {limit!r}")
+    if isinstance(limit, float):
+        if limit == 1.0:
+            return batches
+        if limit > 1.0:
+            raise ValueError(f"{what}={limit!r}: a float is a fraction in [0, 1]; pass an int for a batch count")
+        limit = int(len(batches) * limit)
+    return itertools.islice(batches, limit)
+
+
+def _batch_size(batch) -> int:
+    try:
+        return int(batch["lr"].shape[0])
+    except (KeyError, TypeError, AttributeError, IndexError):
+        return 1
+
+
+def _better(mode: str):
+    if mode not in ("min", "max"):
+        raise ValueError(f'mode must be "min" or "max", got {mode!r}')
+    return (lambda a, b: a < b) if mode == "min" else (lambda a, b: a > b)
+
+
+def _monitored(trainer, monitor: str, who: str) -> float:
+    if monitor not in trainer.callback_metrics:
+        raise RuntimeError(f"{who}(monitor={monitor!r}): no such metric after validation; have "
+                           f"{sorted(trainer.callback_metrics)}")
+    return float(trainer.callback_metrics[monitor])  # the callback's one host read per validation
+
+
+class ModelCheckpoint:
+    """Lightning's ``ModelCheckpoint`` for the built-in trainer (conf/callbacks/model_checkpoint.yaml monitors
+    ``hp_metric``): after each validation inside ``fit`` it saves through the task's ``save_checkpoint`` with the live
+    optimizers and schedulers, keeps the best ``save_top_k`` files (-1: all, 0: none) and deletes the rest;
+    ``save_last`` also writes ``last.ckpt``."""
+
+    def __init__(self, monitor: str = "hp_metric", mode: str = "min", save_top_k: int = 1, save_last: Optional[bool] = None,
+                 dirpath: str = "checkpoints", filename: Optional[str] = None, auto_insert_metric_name: bool = True):
+        self._is_better = _better(mode)
+        self.monitor, self.mode, self.save_top_k, self.save_last = monitor, mode, int(save_top_k), bool(save_last)
+        self.dirpath, self.filename, self.auto_insert_metric_name = dirpath, filename, auto_insert_metric_name
+        self.best_k_models: Dict[str, float] = {}
+        self.best_model_path, self.best_model_score, self.last_model_path = "", None, ""
+
+    def format_checkpoint_name(self, metrics: Dict[str, Any]) -> str:
+        """Lightning's file-name rule: ``{name...}`` becomes ``name={name...}`` (auto_insert_metric_name), a metric
+        that is missing counts as 0, and the default is ``{epoch}-{step}``."""
+        name = self.filename or "{epoch}-{step}"
+        metrics = dict(metrics)
+        for group in dict.fromkeys(re.findall(r"(\{.*?)[:\}]", name)):
+            key = group[1:]
+            name = name.replace(group, (key + "=" if self.auto_insert_metric_name else "") + "{0[" + key + "]")
+            metrics.setdefault(key, 0)
+        return name.format(metrics) + ".ckpt"
+
+    def on_validation_end(self, trainer) -> None:
+        score = _monitored(trainer, self.monitor, "ModelCheckpoint")
+        if math.isnan(score):  # Lightning: NaN is the worst score
+            score = math.inf if self.mode == "min" else -math.inf
+        os.makedirs(self.dirpath, exist_ok=True)
+        k = self.save_top_k
+        worst = (max if self.mode == "min" else min)(self.best_k_models, key=self.best_k_models.get, default=None)
+        if k != 0 and (k < 0 or len(self.best_k_models) < k or self._is_better(score, self.best_k_models[worst])):
+            fields = {"epoch": trainer.current_epoch, "step": trainer.global_step, self.monitor: score}
+            for key in re.findall(r"\{(.*?)[:\}]", self.filename or ""):  # other metrics named by the file name
+                if key not in fields and key in trainer.callback_metrics:
+                    fields[key] = float(trainer.callback_metrics[key])
+            path = os.path.join(self.dirpath, self.format_checkpoint_name(fields))
+            trainer.save_checkpoint(path)
+            self.best_k_models[path] = score
+            if k > 0 and len(self.best_k_models) > k:
+                del self.best_k_models[worst]
+                if worst != path and os.path.exists(worst):
+                    os.remove(worst)
+            best = min if self.mode == "min" else max
+            self.best_model_path = best(self.best_k_models, key=self.best_k_models.get)
+            self.best_model_score = self.best_k_models[self.best_model_path]
+        if self.save_last:
+            self.last_model_path = os.path.join(self.dirpath, "last.ckpt")
+            trainer.save_checkpoint(self.last_model_path)
+
+
+class EarlyStopping:
+    """Lightning's ``EarlyStopping`` (conf/callbacks/early_stopping.yaml): the monitored value improves when it beats the
+    best so far by more than ``min_delta``; after ``patience`` validations in a row without that, or on a NaN / infinite
+    value (``check_finite``), ``fit`` stops after the current epoch."""
+
+    def __init__(self, monitor: str = "hp_metric", mode: str = "min", patience: int = 3, min_delta: float = 0.0,
+                 check_finite: bool = True):
+        self._is_better = _better(mode)
+        self.monitor, self.mode, self.patience, self.check_finite = monitor, mode, int(patience), check_finite
+        self.min_delta = abs(float(min_delta)) * (1.0 if mode == "max" else -1.0)
+        self.best_score = math.inf if mode == "min" else -math.inf
+        self.wait_count, self.stopped_epoch = 0, None
+
+    def on_validation_end(self, trainer) -> None:
+        cur = _monitored(trainer, self.monitor, "EarlyStopping")
+        stop = False
+        if self.check_finite and not math.isfinite(cur):
+            stop = True
+        elif self._is_better(cur - self.min_delta, self.best_score):
+            self.best_score, self.wait_count = cur, 0
+        else:
+            self.wait_count += 1
+            stop = self.wait_count >= self.patience
+        if stop:
+            trainer.should_stop, self.stopped_epoch = True, trainer.current_epoch
 
 
 def _norm_label(track_grad_norm) -> Optional[str]:
@@ -55,7 +198,9 @@ class Trainer:
     def __init__(self, module, num_training_steps: Optional[int] = None, max_epochs: int = 1, max_steps: Optional[int] = None,
                  limit_train_batches=1.0, accumulate_grad_batches: int = 1, datamodule=None, num_gpus: int = 0,
                  num_processes: int = 1, gradient_clip_val: float = 0.0, gradient_clip_algorithm: str = "norm",
-                 track_grad_norm=-1, terminate_on_nan: bool = False):
+                 track_grad_norm=-1, terminate_on_nan: bool = False, check_val_every_n_epoch: int = 1, limit_val_batches=1.0,
+                 limit_test_batches=1.0, num_sanity_val_steps: int = 0, val_check_interval=1.0, callbacks=None,
+                 resume_from_checkpoint: Optional[str] = None):
         if isinstance(accumulate_grad_batches, (dict, list, tuple)):
             raise NotImplementedError("accumulate_grad_batches: Lightning's per-epoch schedules (dict / list) are not "
                                       "implemented; pass one int >= 1")
@@ -68,6 +213,11 @@ class Trainer:
             raise NotImplementedError('gradient_clip_algorithm="value" is not implemented; only "norm"')
         if gradient_clip_algorithm != "norm":
             raise ValueError(f'gradient_clip_algorithm must be "norm" or "value", got {gradient_clip_algorithm!r}')
+        if val_check_interval != 1.0:
+            raise NotImplementedError("val_check_interval: validation inside an epoch is not implemented; only 1.0 "
+                                      "(validate after the epochs check_val_every_n_epoch selects)")
+        if isinstance(check_val_every_n_epoch, bool) or not isinstance(check_val_every_n_epoch, int) or check_val_every_n_epoch < 1:
+            raise ValueError(f"check_val_every_n_epoch must be an int >= 1, got {check_val_every_n_epoch!r}")
         self._norm_label = _norm_label(track_grad_norm)
         self.gradient_clip_val, self.gradient_clip_algorithm = gradient_clip_val, gradient_clip_algorithm
         self.track_grad_norm, self.terminate_on_nan = track_grad_norm, bool(terminate_on_nan)
@@ -81,6 +231,15 @@ class Trainer:
         self.optimizers, self.schedulers = module.configure_optimizers()
         self.nets = [module.generator] + ([module.discriminator] if module.discriminator is not None else [])
         self._param_names: Dict[int, List[str]] = {}
+        self.check_val_every_n_epoch, self.num_sanity_val_steps = check_val_every_n_epoch, int(num_sanity_val_steps)
+        self.limit_val_batches, self.limit_test_batches = limit_val_batches, limit_test_batches
+        self.callbacks = list(callbacks or [])
+        self.callback_metrics: Dict[str, Any] = {}
+        self.should_stop = False
+        self.test_table = self.test_table_nearest = self.test_table_cubic = None
+        self._set_progress(0, 0)
+        if resume_from_checkpoint is not None:
+            self._resume(resume_from_checkpoint)
 
     def _toggle(self, i: int) -> None:
         for j, net in enumerate(self.nets):
@@ -162,9 +321,15 @@ class Trainer:
         if stepping:
             for s in self.schedulers:
                 s["scheduler"].step()
+            self._set_progress(self.current_epoch, self.global_step + 1)  # optimizer 0's steps, as Lightning counts
         return outs
 
-    def fit(self, batches: Iterable[Dict[str, Any]]):
+    def fit(self, batches: Optional[Iterable[Dict[str, Any]]] = None, datamodule=None):
+        """``fit(batches)``: one pass over the iterable.  ``fit(datamodule=dm)`` / ``fit()``: the epoch loop."""
+        if batches is None:
+            return self._fit_epochs(datamodule if datamodule is not None else self.datamodule)
+        if datamodule is not None:
+            raise ValueError("fit: pass either batches (one pass) or datamodule= (the epoch loop), not both")
         outs = []
         if self.accumulate_grad_batches == 1:
             for idx, b in enumerate(batches):
@@ -185,3 +350,146 @@ class Trainer:
             if last:
                 return outs
             cur, idx = nxt, idx + 1
+
+    # -- epochs, validation, test, checkpoints
+    def _set_progress(self, epoch: int, global_step: Optional[int] = None) -> None:
+        self.current_epoch = epoch
+        if global_step is not None:
+            self.global_step = global_step
+        for k, v in (("current_epoch", self.current_epoch), ("global_step", self.global_step)):
+            try:
+                setattr(self.module, k, v)
+            except AttributeError:  # a read-only property of the module
+                pass
+
+    def _steps_done(self) -> bool:
+        return bool(self.max_steps) and self.max_steps > 0 and self.global_step >= self.max_steps
+
+    def _train_epoch(self, batches, outs: List[Any]) -> bool:
+        """One pass over the epoch's batches (batch_idx restarts at 0); True when ``max_steps`` cut it short."""
+        it = iter(_limited(batches, self.limit_train_batches, "limit_train_batches"))
+        ahead = self.accumulate_grad_batches > 1  # the epoch's last batch closes an open accumulation window
+        cur, idx = next(it, _END), 0
+        while cur is not _END:
+            nxt = next(it, _END) if ahead else None
+            outs.append(self.training_batch(cur, idx, last=nxt is _END))
+            if self._steps_done():
+                return True
+            cur, idx = (nxt if ahead else next(it, _END)), idx + 1
+        return False
+
+    def _fit_epochs(self, dm):
+        if dm is None:
+            raise ValueError("fit() without batches needs a datamodule: fit(datamodule=dm) or Trainer(datamodule=dm)")
+        train = dm.train_dataloader()
+        val = dm.val_dataloader() if hasattr(dm, "val_dataloader") and self.limit_val_batches else None  # 0 switches it off
+        if val is not None and self.num_sanity_val_steps:
+            self._eval_loop("val", itertools.islice(val, self.num_sanity_val_steps) if self.num_sanity_val_steps > 0 else val,
+                            discard=True)
+        outs: List[Any] = []
+        self.should_stop = False
+        for epoch in range(self.current_epoch, self.max_epochs):
+            if self._steps_done():
+                break
+            self._set_progress(epoch)
+            if self._train_epoch(train, outs):
+                break
+            if val is not None and (epoch + 1) % self.check_val_every_n_epoch == 0:
+                self._eval_loop("val", _limited(val, self.limit_val_batches, "limit_val_batches"))
+                for cb in self.callbacks:
+                    cb.on_validation_end(self)
+            if self.should_stop:
+                break
+        return outs
+
+    def _eval_loop(self, stage: str, batches, discard: bool = False, per_image: bool = False, baselines: bool = False):
+        """``validation_step`` / ``test_step`` over ``batches`` in eval() under no_grad; the epoch values (device
+        tensors, no host read) go to ``callback_metrics`` and ``module.logged`` unless ``discard`` (the sanity check)."""
+        import torch
+
+        m = self.module
+        step = m.validation_step if stage == "val" else m.test_step
+        was_training = getattr(m, "training", True)
+        logged = getattr(m, "logged", None)
+        keep = dict(logged) if discard and logged is not None else None
+        sums: Dict[str, Any] = {}
+        weight: Dict[str, int] = {}
+        outputs, tables = [], {"sr": [], "nearest": [], "cubic": []}
+        m.eval()
+        try:
+            with torch.no_grad():
+                for idx, batch in enumerate(batches):
+                    out = step(batch, idx)
+                    bs = _batch_size(batch)
+                    if per_image:
+                        maps = [("sr", out["sr"])] + ([("nearest", batch["nearest"]), ("cubic", batch["cubic"])] if baselines else [])
+                        for name, x in maps:
+                            tables[name].append(m.metrics.per_image(x, batch["hr"], batch["original_data"], batch["mask"],
+                                                                    batch.get("min"), batch.get("max")))
+                    scalars = {k: v for k, v in out.items() if isinstance(v, torch.Tensor) and v.numel() == 1}
+                    for k, v in scalars.items():
+                        v = v.detach().reshape(()).to(torch.float64) * bs
+                        sums[k] = v if k not in sums else sums[k] + v
+                        weight[k] = weight.get(k, 0) + bs
+                    if stage == "val":
+                        outputs.append(scalars)
+                if stage == "val" and outputs and not discard:
+                    m.validation_epoch_end(outputs)
+        finally:
+            m.train(was_training)
+        if discard:
+            if keep is not None:
+                logged.clear()
+                logged.update(keep)
+            return {}
+        metrics = {k: s / weight[k] for k, s in sums.items()}
+        if stage == "val" and logged is not None and "hp_metric" in logged:
+            metrics["hp_metric"] = logged["hp_metric"]
+        if logged is not None:
+            logged.update(metrics)
+        self.callback_metrics.update(metrics)
+        if per_image:
+            cat = lambda rows: torch.cat(rows, 0) if rows else None  # noqa: E731
+            self.test_table, self.test_table_nearest, self.test_table_cubic = (cat(tables[k]) for k in ("sr", "nearest", "cubic"))
+        return metrics
+
+    def _loader(self, stage: str, batches, datamodule):
+        if batches is not None:
+            return batches
+        dm = datamodule if datamodule is not None else self.datamodule
+        if dm is None:
+            raise ValueError(f"{stage}: pass batches, datamodule= or Trainer(datamodule=...)")
+        loader = getattr(dm, "val_dataloader" if stage == "validate" else "test_dataloader")()
+        if loader is None:
+            raise ValueError(f"{stage}: the datamodule has no {stage} batches")
+        return loader
+
+    @staticmethod
+    def _floats(metrics: Dict[str, Any]) -> List[Dict[str, float]]:
+        import torch
+
+        if not metrics:
+            return [{}]
+        vals = torch.stack([torch.as_tensor(v, dtype=torch.float64).reshape(()) for v in metrics.values()]).tolist()
+        return [dict(zip(metrics, vals))]  # one host read
+
+    def validate(self, batches=None, datamodule=None) -> List[Dict[str, float]]:
+        """One validation epoch on its own (no callbacks); Lightning's return shape, one host read at the end."""
+        loader = _limited(self._loader("validate", batches, datamodule), self.limit_val_batches, "limit_val_batches")
+        return self._floats(self._eval_loop("val", loader))
+
+    def test(self, batches=None, datamodule=None, per_image: bool = False, baselines: bool = False) -> List[Dict[str, float]]:
+        if baselines and not per_image:
+            raise ValueError("test(baselines=True) fills the nearest / cubic per-image tables: it needs per_image=True")
+        loader = _limited(self._loader("test", batches, datamodule), self.limit_test_batches, "limit_test_batches")
+        return self._floats(self._eval_loop("test", loader, per_image=per_image, baselines=baselines))
+
+    def save_checkpoint(self, path: str):
+        return self.module.save_checkpoint(path, epoch=self.current_epoch, global_step=self.global_step,
+                                           optimizers=self.optimizers, schedulers=self.schedulers)
+
+    def _resume(self, path: str) -> None:
+        from .checkpoint import restore_training_state
+
+        epoch, global_step = restore_training_state(self.module, path, self.optimizers, self.schedulers)
+        self._set_progress(epoch + 1, global_step)  # the file was written after its epoch: go on with the next

@@ -302,10 +302,9 @@ struct Denorm {
   double scale = 1.0, add = 0.0;
 };
 
-__device__ __forceinline__ void masked_values(const ClimsrMetricsDesc& d, long i, Denorm& dn, float& pn, float& tn, double& pd,
-                                              double& td) {
-  const int hw = d.h * d.w;
-  const int t = (int)(i / hw);
+// Pixel i (flat index over the batch) of sample t: the masked normalised pair (pn, tn) and the masked denormalised pair (pd, td).
+__device__ __forceinline__ void masked_values_at(const ClimsrMetricsDesc& d, long i, int t, Denorm& dn, float& pn, float& tn,
+                                                 double& pd, double& td) {
   const bool land = d.mask[i] != 0.f;  // `(~mask.bool())` -> 0
   const float sr = d.sr[i];
   pn = land ? sr : 0.f;
@@ -328,49 +327,63 @@ __device__ __forceinline__ void masked_values(const ClimsrMetricsDesc& d, long i
   td = land ? (double)d.original[i] : 0.0;
 }
 
-__global__ void __launch_bounds__(256) metrics_partial_kernel(ClimsrMetricsDesc d) {
+__device__ __forceinline__ void masked_values(const ClimsrMetricsDesc& d, long i, Denorm& dn, float& pn, float& tn, double& pd,
+                                              double& td) {
+  const int hw = d.h * d.w;
+  masked_values_at(d, i, (int)(i / hw), dn, pn, tn, pd, td);
+}
+
+// One thread's running sums and extrema of the fused pass.
+struct PixelAcc {
   double acc[P_NSUM];
+  double tdmin, tdmax;
+  float pnmin, pnmax, tnmin, tnmax;
+};
+
+__device__ __forceinline__ void acc_init(PixelAcc& a) {
 #pragma unroll
-  for (int k = 0; k < P_NSUM; ++k) acc[k] = 0.0;
-  double tdmin = INFINITY, tdmax = -INFINITY;
-  float pnmin = INFINITY, pnmax = -INFINITY, tnmin = INFINITY, tnmax = -INFINITY;
-  const long total = (long)d.n * d.h * d.w;
+  for (int k = 0; k < P_NSUM; ++k) a.acc[k] = 0.0;
+  a.tdmin = INFINITY;
+  a.tdmax = -INFINITY;
+  a.pnmin = a.tnmin = INFINITY;
+  a.pnmax = a.tnmax = -INFINITY;
+}
+
+__device__ __forceinline__ void acc_pixel(const ClimsrMetricsDesc& d, PixelAcc& a, float pn, float tn, double pd, double td) {
   const float MEPS = 1.17e-06f;  // torchmetrics MAPE / SMAPE epsilon
-  Denorm dn_cache;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    float pn, tn;
-    double pd, td;
-    masked_values(d, i, dn_cache, pn, tn, pd, td);
-    double dd = pd - td;
-    double ad = fabs(dd);
-    acc[P_ABS] += ad;
-    acc[P_SQ] += dd * dd;
+  double dd = pd - td;
+  double ad = fabs(dd);
+  a.acc[P_ABS] += ad;
+  a.acc[P_SQ] += dd * dd;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) acc[P_ACC0 + k] += (ad <= (double)d.acc_eps[k]) ? 1.0 : 0.0;
-    float dn = fabsf(pn - tn);
-    acc[P_MAPE] += (double)(dn / fmaxf(fabsf(tn), MEPS));
-    acc[P_SMAPE] += ad / fmax(fabs(td) + fabs(pd), (double)MEPS);
-    acc[P_T] += td;
-    acc[P_TT] += td * td;
-    acc[P_L1N] += (double)dn;
-    tdmin = fmin(tdmin, td);
-    tdmax = fmax(tdmax, td);
-    pnmin = fminf(pnmin, pn);
-    pnmax = fmaxf(pnmax, pn);
-    tnmin = fminf(tnmin, tn);
-    tnmax = fmaxf(tnmax, tn);
-  }
+  for (int k = 0; k < 8; ++k) a.acc[P_ACC0 + k] += (ad <= (double)d.acc_eps[k]) ? 1.0 : 0.0;
+  float dn = fabsf(pn - tn);
+  a.acc[P_MAPE] += (double)(dn / fmaxf(fabsf(tn), MEPS));
+  a.acc[P_SMAPE] += ad / fmax(fabs(td) + fabs(pd), (double)MEPS);
+  a.acc[P_T] += td;
+  a.acc[P_TT] += td * td;
+  a.acc[P_L1N] += (double)dn;
+  a.tdmin = fmin(a.tdmin, td);
+  a.tdmax = fmax(a.tdmax, td);
+  a.pnmin = fminf(a.pnmin, pn);
+  a.pnmax = fmaxf(a.pnmax, pn);
+  a.tnmin = fminf(a.tnmin, tn);
+  a.tnmax = fmaxf(a.tnmax, tn);
+}
+
+// The 256 threads' PixelAcc -> dst[P_SLOTS]: shuffle tree per wave, then the 4 waves in order.
+__device__ __forceinline__ void acc_block_store(const PixelAcc& a, double* __restrict__ dst) {
   __shared__ double sh[P_SLOTS][4];
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   double v[P_SLOTS];
 #pragma unroll
-  for (int k = 0; k < P_NSUM; ++k) v[k] = acc[k];
-  v[P_TD_MIN] = tdmin;
-  v[P_TD_MAX] = tdmax;
-  v[P_PN_MIN] = pnmin;
-  v[P_PN_MAX] = pnmax;
-  v[P_TN_MIN] = tnmin;
-  v[P_TN_MAX] = tnmax;
+  for (int k = 0; k < P_NSUM; ++k) v[k] = a.acc[k];
+  v[P_TD_MIN] = a.tdmin;
+  v[P_TD_MAX] = a.tdmax;
+  v[P_PN_MIN] = a.pnmin;
+  v[P_PN_MAX] = a.pnmax;
+  v[P_TN_MIN] = a.tnmin;
+  v[P_TN_MAX] = a.tnmax;
 #pragma unroll
   for (int k = 0; k < P_SLOTS; ++k) {
     double x = v[k];
@@ -392,8 +405,22 @@ __global__ void __launch_bounds__(256) metrics_partial_kernel(ClimsrMetricsDesc 
       else if ((k - P_NSUM) % 2 == 0) x = fmin(x, y);
       else x = fmax(x, y);
     }
-    d.workspace[(long)blockIdx.x * P_SLOTS + k] = x;
+    dst[k] = x;
   }
+}
+
+__global__ void __launch_bounds__(256) metrics_partial_kernel(ClimsrMetricsDesc d) {
+  PixelAcc a;
+  acc_init(a);
+  const long total = (long)d.n * d.h * d.w;
+  Denorm dn_cache;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    float pn, tn;
+    double pd, td;
+    masked_values(d, i, dn_cache, pn, tn, pd, td);
+    acc_pixel(d, a, pn, tn, pd, td);
+  }
+  acc_block_store(a, d.workspace + (long)blockIdx.x * P_SLOTS);
 }
 
 __device__ __forceinline__ double combine(int k, double x, double y) {
@@ -415,14 +442,15 @@ __global__ void __launch_bounds__(1024) metrics_stats_kernel(ClimsrMetricsDesc d
 
 // SSIM over the masked normalised maps: 5 Gaussian-filtered maps (p, t, p², t², pt), reflect padding
 // (only the cropped interior [5, h-5) x [5, w-5) is averaged, whose windows never touch the pad).
-__global__ void __launch_bounds__(256) ssim_kernel(ClimsrMetricsDesc d) {
-  __shared__ float sp[SSIM_IN][SSIM_IN + 1], st[SSIM_IN][SSIM_IN + 1];
-  __shared__ float hsum[5][SSIM_IN][SSIM_T + 1];
-  __shared__ float g[SSIM_K];
-  __shared__ double red[4];
-  const int oh = d.h - 2 * SSIM_R, ow = d.w - 2 * SSIM_R;
-  const int tiles_y = (oh + SSIM_T - 1) / SSIM_T, tiles_x = (ow + SSIM_T - 1) / SSIM_T;
-  const long ntiles = (long)d.n * tiles_y * tiles_x;
+struct SsimLds {
+  float sp[SSIM_IN][SSIM_IN + 1], st[SSIM_IN][SSIM_IN + 1];
+  float hsum[5][SSIM_IN][SSIM_T + 1];
+  float g[SSIM_K];
+  double red[4];
+};
+
+// The window weights; visible to the block after the barrier that opens ssim_tile.
+__device__ __forceinline__ void ssim_gaussian(SsimLds& L) {
   if (threadIdx.x < SSIM_K) {  // torchmetrics _gaussian: exp(-(dist/sigma)^2 / 2), normalised
     float s = 0.f, gv = 0.f;
     for (int i = 0; i < SSIM_K; ++i) {
@@ -431,72 +459,122 @@ __global__ void __launch_bounds__(256) ssim_kernel(ClimsrMetricsDesc d) {
       s += e;
       if (i == (int)threadIdx.x) gv = e;
     }
-    g[threadIdx.x] = gv / s;
+    L.g[threadIdx.x] = gv / s;
   }
+}
+
+// data_range=None: the larger of the two maps' ranges -> the stabilisers c1, c2.
+__device__ __forceinline__ void ssim_consts(double pnmin, double pnmax, double tnmin, double tnmax, float& c1, float& c2) {
+  const float dr = fmaxf((float)pnmax - (float)pnmin, (float)tnmax - (float)tnmin);
+  c1 = (0.01f * dr) * (0.01f * dr);
+  c2 = (0.03f * dr) * (0.03f * dr);
+}
+
+// The whole block's sum of the threads' `part` (shuffle tree per wave, then the 4 waves in order); valid in thread 0.
+__device__ __forceinline__ double ssim_block_sum(SsimLds& L, double part) {
+  for (int o = 32; o > 0; o >>= 1) part += __shfl_down(part, o);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) L.red[threadIdx.x >> 6] = part;
+  __syncthreads();
+  return L.red[0] + L.red[1] + L.red[2] + L.red[3];
+}
+
+// One 32x32 tile of sample b's cropped SSIM map, origin (oy0, ox0): each thread adds its pixels' indices to `part`.
+__device__ __forceinline__ void ssim_tile(const ClimsrMetricsDesc& d, SsimLds& L, int b, int oy0, int ox0, float c1, float c2,
+                                          double& part) {
+  auto& sp = L.sp;
+  auto& st = L.st;
+  auto& hsum = L.hsum;
+  auto& g = L.g;
+  const int oh = d.h - 2 * SSIM_R, ow = d.w - 2 * SSIM_R;
+  __syncthreads();
+  for (int e = threadIdx.x; e < SSIM_IN * SSIM_IN; e += blockDim.x) {
+    int iy = e / SSIM_IN, ix = e % SSIM_IN;
+    int gy = oy0 + iy, gx = ox0 + ix;  // input row/col (crop offset cancels the window radius)
+    float pn = 0.f, tn = 0.f;
+    if (gy < d.h && gx < d.w) {  // normalised maps only: SSIM never sees the denormalised values
+      long i = ((long)b * d.h + gy) * d.w + gx;
+      if (d.mask[i] != 0.f) {
+        pn = d.sr[i];
+        tn = d.hr[i];
+      }
+    }
+    sp[iy][ix] = pn;
+    st[iy][ix] = tn;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < SSIM_IN * SSIM_T; e += blockDim.x) {
+    int iy = e / SSIM_T, ox = e % SSIM_T;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f;
+#pragma unroll
+    for (int k = 0; k < SSIM_K; ++k) {
+      float p = sp[iy][ox + k], q = st[iy][ox + k], w = g[k];
+      a0 += w * p;
+      a1 += w * q;
+      a2 += w * (p * p);
+      a3 += w * (q * q);
+      a4 += w * (p * q);
+    }
+    hsum[0][iy][ox] = a0;
+    hsum[1][iy][ox] = a1;
+    hsum[2][iy][ox] = a2;
+    hsum[3][iy][ox] = a3;
+    hsum[4][iy][ox] = a4;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < SSIM_T * SSIM_T; e += blockDim.x) {
+    int oy = e / SSIM_T, ox = e % SSIM_T;
+    if (oy0 + oy >= oh || ox0 + ox >= ow) continue;
+    float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < SSIM_K; ++k) {
+      float w = g[k];
+#pragma unroll
+      for (int q = 0; q < 5; ++q) m[q] += w * hsum[q][oy + k][ox];
+    }
+    float mu_p2 = m[0] * m[0], mu_t2 = m[1] * m[1], mu_pt = m[0] * m[1];
+    float s_p = m[2] - mu_p2, s_t = m[3] - mu_t2, s_pt = m[4] - mu_pt;
+    float upper = 2.f * s_pt + c2, lower = s_p + s_t + c2;
+    part += (double)(((2.f * mu_pt + c1) * upper) / ((mu_p2 + mu_t2 + c1) * lower));
+  }
+}
+
+__global__ void __launch_bounds__(256) ssim_kernel(ClimsrMetricsDesc d) {
+  __shared__ SsimLds L;
+  const int oh = d.h - 2 * SSIM_R, ow = d.w - 2 * SSIM_R;
+  const int tiles_y = (oh + SSIM_T - 1) / SSIM_T, tiles_x = (ow + SSIM_T - 1) / SSIM_T;
+  const long ntiles = (long)d.n * tiles_y * tiles_x;
+  ssim_gaussian(L);
+  float c1, c2;
   const double* stats = d.workspace + WS_STATS;
-  const float dr = fmaxf((float)stats[P_PN_MAX] - (float)stats[P_PN_MIN], (float)stats[P_TN_MAX] - (float)stats[P_TN_MIN]);
-  const float c1 = (0.01f * dr) * (0.01f * dr), c2 = (0.03f * dr) * (0.03f * dr);
+  ssim_consts(stats[P_PN_MIN], stats[P_PN_MAX], stats[P_TN_MIN], stats[P_TN_MAX], c1, c2);
   double part = 0.0;
   for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int b = (int)(tile / (tiles_y * tiles_x));
     const int r = (int)(tile - (long)b * tiles_y * tiles_x);
-    const int oy0 = (r / tiles_x) * SSIM_T, ox0 = (r % tiles_x) * SSIM_T;  // cropped-output origin
-    __syncthreads();
-    for (int e = threadIdx.x; e < SSIM_IN * SSIM_IN; e += blockDim.x) {
-      int iy = e / SSIM_IN, ix = e % SSIM_IN;
-      int gy = oy0 + iy, gx = ox0 + ix;  // input row/col (crop offset cancels the window radius)
-      float pn = 0.f, tn = 0.f;
-      if (gy < d.h && gx < d.w) {  // normalised maps only: SSIM never sees the denormalised values
-        long i = ((long)b * d.h + gy) * d.w + gx;
-        if (d.mask[i] != 0.f) {
-          pn = d.sr[i];
-          tn = d.hr[i];
-        }
-      }
-      sp[iy][ix] = pn;
-      st[iy][ix] = tn;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < SSIM_IN * SSIM_T; e += blockDim.x) {
-      int iy = e / SSIM_T, ox = e % SSIM_T;
-      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f;
-#pragma unroll
-      for (int k = 0; k < SSIM_K; ++k) {
-        float p = sp[iy][ox + k], q = st[iy][ox + k], w = g[k];
-        a0 += w * p;
-        a1 += w * q;
-        a2 += w * (p * p);
-        a3 += w * (q * q);
-        a4 += w * (p * q);
-      }
-      hsum[0][iy][ox] = a0;
-      hsum[1][iy][ox] = a1;
-      hsum[2][iy][ox] = a2;
-      hsum[3][iy][ox] = a3;
-      hsum[4][iy][ox] = a4;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < SSIM_T * SSIM_T; e += blockDim.x) {
-      int oy = e / SSIM_T, ox = e % SSIM_T;
-      if (oy0 + oy >= oh || ox0 + ox >= ow) continue;
-      float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int k = 0; k < SSIM_K; ++k) {
-        float w = g[k];
-#pragma unroll
-        for (int q = 0; q < 5; ++q) m[q] += w * hsum[q][oy + k][ox];
-      }
-      float mu_p2 = m[0] * m[0], mu_t2 = m[1] * m[1], mu_pt = m[0] * m[1];
-      float s_p = m[2] - mu_p2, s_t = m[3] - mu_t2, s_pt = m[4] - mu_pt;
-      float upper = 2.f * s_pt + c2, lower = s_p + s_t + c2;
-      part += (double)(((2.f * mu_pt + c1) * upper) / ((mu_p2 + mu_t2 + c1) * lower));
-    }
+    ssim_tile(d, L, b, (r / tiles_x) * SSIM_T, (r % tiles_x) * SSIM_T, c1, c2, part);  // cropped-output origin
   }
-  for (int o = 32; o > 0; o >>= 1) part += __shfl_down(part, o);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
-  __syncthreads();
-  if (threadIdx.x == 0) d.workspace[WS_SSIM + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  const double sum = ssim_block_sum(L, part);
+  if (threadIdx.x == 0) d.workspace[WS_SSIM + blockIdx.x] = sum;
+}
+
+// The 17 results of `nimg` samples of h x w from their combined slots s[P_SLOTS] and the sum of their SSIM maps.
+__device__ __forceinline__ void metrics_formulas(const ClimsrMetricsDesc& d, const double* s, double ssim_sum, int nimg,
+                                                 double* out) {
+  const double n = (double)nimg * d.h * d.w;
+  for (int k = 0; k < 8; ++k) out[k] = s[P_ACC0 + k] / n;  // RegressionAccuracy: correct / total
+  const double mse = s[P_SQ] / n;
+  const double range = s[P_TD_MAX] - s[P_TD_MIN];           // PSNR(data_range=None): target max - min
+  out[8] = (2.0 * log(range) - log(mse)) * (10.0 / log(10.0));
+  out[9] = ssim_sum / ((double)nimg * (d.h - 2 * SSIM_R) * (d.w - 2 * SSIM_R));
+  out[10] = s[P_ABS] / n;       // MAE
+  out[11] = mse;                // MSE
+  out[12] = sqrt(mse);          // RMSE (MeanSquaredError(squared=False))
+  out[13] = s[P_MAPE] / n;      // MAPE on the normalised maps
+  out[14] = 2.0 * s[P_SMAPE] / n;
+  const double mean_t = s[P_T] / n;  // R2Score: 1 - SS_res / (sum t^2 - sum t * mean t)
+  out[15] = 1.0 - s[P_SQ] / (s[P_TT] - s[P_T] * mean_t);
+  out[16] = s[P_L1N] / n;       // normalised L1 (`{prefix}/normalized_loss`, `{prefix}/loss`)
 }
 
 __global__ void __launch_bounds__(SSIM_BLOCKS) metrics_final_kernel(ClimsrMetricsDesc d, int ssim_blocks) {
@@ -508,22 +586,7 @@ __global__ void __launch_bounds__(SSIM_BLOCKS) metrics_final_kernel(ClimsrMetric
     __syncthreads();
   }
   if (threadIdx.x != 0) return;
-  const double* s = d.workspace + WS_STATS;
-  const double n = (double)d.n * d.h * d.w;
-  double* out = d.out;
-  for (int k = 0; k < 8; ++k) out[k] = s[P_ACC0 + k] / n;  // RegressionAccuracy: correct / total
-  const double mse = s[P_SQ] / n;
-  const double range = s[P_TD_MAX] - s[P_TD_MIN];           // PSNR(data_range=None): target max - min
-  out[8] = (2.0 * log(range) - log(mse)) * (10.0 / log(10.0));
-  out[9] = sh[0] / ((double)d.n * (d.h - 2 * SSIM_R) * (d.w - 2 * SSIM_R));
-  out[10] = s[P_ABS] / n;       // MAE
-  out[11] = mse;                // MSE
-  out[12] = sqrt(mse);          // RMSE (MeanSquaredError(squared=False))
-  out[13] = s[P_MAPE] / n;      // MAPE on the normalised maps
-  out[14] = 2.0 * s[P_SMAPE] / n;
-  const double mean_t = s[P_T] / n;  // R2Score: 1 - SS_res / (sum t^2 - sum t * mean t)
-  out[15] = 1.0 - s[P_SQ] / (s[P_TT] - s[P_T] * mean_t);
-  out[16] = s[P_L1N] / n;       // normalised L1 (`{prefix}/normalized_loss`, `{prefix}/loss`)
+  metrics_formulas(d, d.workspace + WS_STATS, sh[0], d.n, d.out);
 }
 
 extern "C" size_t climsr_sr_metrics_workspace(void) { return (size_t)(WS_SSIM + SSIM_BLOCKS) * sizeof(double); }
@@ -544,6 +607,112 @@ extern "C" int climsr_sr_metrics(const ClimsrMetricsDesc* d, void* stream) {
   hipLaunchKernelGGL(ssim_kernel, dim3(sb), dim3(256), 0, s, dd);
   hipLaunchKernelGGL(metrics_final_kernel, dim3(1), dim3(SSIM_BLOCKS), 0, s, dd, sb);
   return check_launch("sr_metrics");
+}
+
+// ------------------------------------------------------------------------------------------
+// The same 17 results per image (LogImagesCallback._metrics_per_image, core/callbacks.py:223-246): row t is what
+// climsr_sr_metrics defines for the one-image batch {t}.  Three launches whatever n: (1) the fused pass, where image t
+// is split over pi_blocks(h, w) workgroups whose partials go to workspace slot (t, block); (2) SSIM, one workgroup per
+// (t, 32x32 tile), which first folds image t's four range slots and writes its sum to slot (t, tile); (3) one
+// workgroup per image folds slots and tile sums in index order and applies the formulas.  The split depends on (h, w)
+// only and no workgroup reads another image's slots, so a row does not depend on n or on the image's position.
+// ------------------------------------------------------------------------------------------
+namespace {
+constexpr int PI_PIX = 2048;  // pixels per workgroup of the fused pass (8 per thread)
+constexpr long PI_MAX_GROUPS = 1L << 23;  // 256-thread workgroups per launch: thread ids stay below 2^31
+inline long pi_blocks(int h, int w) { return ((long)h * w + PI_PIX - 1) / PI_PIX; }
+inline long pi_tiles(int h, int w) {
+  return (long)((h - 2 * SSIM_R + SSIM_T - 1) / SSIM_T) * ((w - 2 * SSIM_R + SSIM_T - 1) / SSIM_T);
+}
+}  // namespace
+
+// Slot k over the nb block partials of one image: lane l folds partials l, l + 64, ... in index order, then the fixed
+// shuffle tree.  Whole wave; valid in lane 0.
+__device__ __forceinline__ double pi_fold(const double* __restrict__ part, int nb, int k, int lane) {
+  double x = k < P_NSUM ? 0.0 : ((k - P_NSUM) % 2 == 0 ? (double)INFINITY : -(double)INFINITY);
+  for (int b = lane; b < nb; b += 64) x = combine(k, x, part[(long)b * P_SLOTS + k]);
+  for (int o = 32; o > 0; o >>= 1) x = combine(k, x, __shfl_down(x, o));
+  return x;
+}
+
+__global__ void __launch_bounds__(256) pi_partial_kernel(ClimsrMetricsDesc d, int nb, long stride) {
+  const int t = blockIdx.x / nb, b = blockIdx.x - t * nb;
+  const long hw = (long)d.h * d.w, base = (long)t * hw;
+  PixelAcc a;
+  acc_init(a);
+  Denorm dn_cache;
+  for (long p = (long)b * 256 + threadIdx.x; p < hw; p += (long)nb * 256) {
+    float pn, tn;
+    double pd, td;
+    masked_values_at(d, base + p, t, dn_cache, pn, tn, pd, td);
+    acc_pixel(d, a, pn, tn, pd, td);
+  }
+  acc_block_store(a, d.workspace + (long)t * stride + (long)b * P_SLOTS);
+}
+
+__global__ void __launch_bounds__(256) pi_ssim_kernel(ClimsrMetricsDesc d, int nb, int tiles, long stride) {
+  __shared__ SsimLds L;
+  __shared__ double rng[4];
+  const int tiles_x = (d.w - 2 * SSIM_R + SSIM_T - 1) / SSIM_T;
+  const int t = blockIdx.x / tiles, r = blockIdx.x - t * tiles;
+  double* img = d.workspace + (long)t * stride;
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  ssim_gaussian(L);
+  const double x = pi_fold(img, nb, P_PN_MIN + wv, lane);  // wave 0..3: pn min, pn max, tn min, tn max
+  if (lane == 0) rng[wv] = x;
+  __syncthreads();
+  float c1, c2;
+  ssim_consts(rng[0], rng[1], rng[2], rng[3], c1, c2);
+  double part = 0.0;
+  ssim_tile(d, L, t, (r / tiles_x) * SSIM_T, (r % tiles_x) * SSIM_T, c1, c2, part);
+  const double sum = ssim_block_sum(L, part);
+  if (threadIdx.x == 0) img[(long)nb * P_SLOTS + r] = sum;
+}
+
+__global__ void __launch_bounds__(256) pi_final_kernel(ClimsrMetricsDesc d, int nb, int tiles, long stride) {
+  __shared__ double s[P_SLOTS + 1];
+  const int t = blockIdx.x;
+  const double* img = d.workspace + (long)t * stride;
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int k = wv; k <= P_SLOTS; k += 4) {  // k == P_SLOTS: the SSIM tile sums
+    double x;
+    if (k < P_SLOTS) {
+      x = pi_fold(img, nb, k, lane);
+    } else {
+      x = 0.0;
+      for (int i = lane; i < tiles; i += 64) x += img[(long)nb * P_SLOTS + i];
+      for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o);
+    }
+    if (lane == 0) s[k] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) metrics_formulas(d, s, s[P_SLOTS], 1, d.out + (long)t * CLIMSR_SR_METRICS);
+}
+
+extern "C" size_t climsr_sr_metrics_per_image_workspace(int n, int h, int w) {
+  if (n <= 0 || h < SSIM_K || w < SSIM_K) return 0;
+  return (size_t)n * (size_t)(pi_blocks(h, w) * P_SLOTS + pi_tiles(h, w)) * sizeof(double);
+}
+
+extern "C" int climsr_sr_metrics_per_image(const ClimsrMetricsDesc* d, void* stream) {
+  if (!d || !d->sr || !d->hr || !d->original || !d->mask || !d->workspace || !d->out || d->n <= 0 ||
+      d->h < SSIM_K || d->w < SSIM_K || (d->method == 0 && (!d->min || !d->max)) || d->method < 0 || d->method > 2) {
+    set_error("sr_metrics_per_image: bad args (h, w >= %d for the 11x11 SSIM window; min/max needed for minmax)", SSIM_K);
+    return CLIMSR_EINVAL;
+  }
+  const long nb = pi_blocks(d->h, d->w), tiles = pi_tiles(d->h, d->w);
+  if (d->n * nb > PI_MAX_GROUPS || d->n * tiles > PI_MAX_GROUPS) {
+    set_error("sr_metrics_per_image: n=%d images of %dx%d need more than %ld workgroups per launch; split the batch", d->n,
+              d->h, d->w, PI_MAX_GROUPS);
+    return CLIMSR_EINVAL;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const ClimsrMetricsDesc dd = *d;
+  const long stride = nb * P_SLOTS + tiles;
+  hipLaunchKernelGGL(pi_partial_kernel, dim3((unsigned)(d->n * nb)), dim3(256), 0, s, dd, (int)nb, stride);
+  hipLaunchKernelGGL(pi_ssim_kernel, dim3((unsigned)(d->n * tiles)), dim3(256), 0, s, dd, (int)nb, (int)tiles, stride);
+  hipLaunchKernelGGL(pi_final_kernel, dim3(d->n), dim3(256), 0, s, dd, (int)nb, (int)tiles, stride);
+  return check_launch("sr_metrics_per_image");
 }
 
 // ------------------------------------------------------------------------------------------

@@ -28,6 +28,7 @@ from .._lib import MetricsDesc, check, ptr
 ACC_EPS = (0.1, 0.25, 0.5, 0.75, 1.0, 1.25, 1.5, 2.0)  # task.py:297-304
 METRIC_KEYS = ("acc@0.1", "acc@0.25", "acc@0.5", "acc@0.75", "acc@1", "acc@01.25", "acc@1.5", "acc@2", "psnr", "ssim",
                "mae", "mse", "rmse", "mape", "smape", "r2")  # task.py:313-330 (the reference's own key spelling)
+PER_IMAGE_KEYS = METRIC_KEYS + ("normalized_loss",)  # the columns of SRMetrics.per_image
 
 
 class SRMetrics:
@@ -40,10 +41,10 @@ class SRMetrics:
         self.zscore = (float(zscore_mean), float(zscore_std))
         self.acc_eps = tuple(float(e) for e in acc_eps)
         self._ws = None
+        self._ws_pi = None  # per_image's workspace: grows with n * h * w
 
-    def raw(self, sr: Tensor, hr: Tensor, original: Tensor, mask: Tensor, min_vals: Optional[Tensor] = None,
-            max_vals: Optional[Tensor] = None) -> Tensor:
-        """The [17] float64 device result vector (METRIC_KEYS + normalised L1)."""
+    def _desc(self, sr, hr, original, mask, min_vals, max_vals):
+        """Checked, contiguous float32 inputs as a MetricsDesc without workspace / out, plus the tensors it points at."""
         if not sr.is_cuda:
             raise RuntimeError("SRMetrics runs in libclimsr_hip.so: inputs must be CUDA tensors")
         n, c, h, w = sr.shape
@@ -58,16 +59,43 @@ class SRMetrics:
                 raise ValueError("min-max denormalisation needs the batch's min / max")
             mn = torch.as_tensor(min_vals, dtype=torch.float64).to(dev).reshape(n).contiguous()
             mx = torch.as_tensor(max_vals, dtype=torch.float64).to(dev).reshape(n).contiguous()
+        d = MetricsDesc(sr=ptr(sr_), hr=ptr(hr_), original=ptr(orig_), mask=ptr(mask_), min=ptr(mn), max=ptr(mx),
+                        range_a=self.range[0], range_b=self.range[1], eps=1e-8,
+                        zs_mean=self.zscore[0], zs_std=self.zscore[1], acc_eps=(ctypes.c_float * 8)(*self.acc_eps),
+                        n=n, h=h, w=w, method=self.method)
+        return d, (sr_, hr_, orig_, mask_, mn, mx)
+
+    def raw(self, sr: Tensor, hr: Tensor, original: Tensor, mask: Tensor, min_vals: Optional[Tensor] = None,
+            max_vals: Optional[Tensor] = None) -> Tensor:
+        """The [17] float64 device result vector (METRIC_KEYS + normalised L1)."""
+        d, _alive = self._desc(sr, hr, original, mask, min_vals, max_vals)
+        dev = sr.device
         L = _lib.load()
         nbytes = L.climsr_sr_metrics_workspace()
         if self._ws is None or self._ws.device != dev:
             self._ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
         out = torch.empty(_lib.SR_METRICS, dtype=torch.float64, device=dev)
-        d = MetricsDesc(sr=ptr(sr_), hr=ptr(hr_), original=ptr(orig_), mask=ptr(mask_), min=ptr(mn), max=ptr(mx),
-                        workspace=ptr(self._ws), out=ptr(out), range_a=self.range[0], range_b=self.range[1], eps=1e-8,
-                        zs_mean=self.zscore[0], zs_std=self.zscore[1], acc_eps=(ctypes.c_float * 8)(*self.acc_eps),
-                        n=n, h=h, w=w, method=self.method)
+        d.workspace, d.out = ptr(self._ws), ptr(out)
         check(L.climsr_sr_metrics(ctypes.byref(d), _lib.stream_ptr(dev)), "sr_metrics")
+        return out
+
+    def per_image(self, sr: Tensor, hr: Tensor, original: Tensor, mask: Tensor, min_vals: Optional[Tensor] = None,
+                  max_vals: Optional[Tensor] = None) -> Tensor:
+        """[n, 17] float64 on the device (columns: PER_IMAGE_KEYS): row t is what ``raw`` defines for the one-image batch
+        ``t:t+1`` -- the reference's ``LogImagesCallback._metrics_per_image`` (core/callbacks.py:223-246) for a whole
+        batch in one ``climsr_sr_metrics_per_image`` call (3 launches whatever n).  A row is bit-identical whatever the
+        batch around it; an all-sea tile gets the IEEE result of its empty sums (NaN / inf) and touches no other row."""
+        d, _alive = self._desc(sr, hr, original, mask, min_vals, max_vals)
+        dev = sr.device
+        L = _lib.load()
+        nbytes = L.climsr_sr_metrics_per_image_workspace(d.n, d.h, d.w)
+        if nbytes == 0:
+            raise ValueError(f"SRMetrics.per_image needs n >= 1 and h, w >= 11 (the SSIM window), got {tuple(sr.shape)}")
+        if self._ws_pi is None or self._ws_pi.device != dev or self._ws_pi.numel() * 8 < nbytes:
+            self._ws_pi = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        out = torch.empty(d.n, _lib.SR_METRICS, dtype=torch.float64, device=dev)
+        d.workspace, d.out = ptr(self._ws_pi), ptr(out)
+        check(L.climsr_sr_metrics_per_image(ctypes.byref(d), _lib.stream_ptr(dev)), "sr_metrics_per_image")
         return out
 
     def __call__(self, sr: Tensor, hr: Tensor, original: Tensor, mask: Tensor, min_vals: Optional[Tensor] = None,

@@ -455,6 +455,11 @@ typedef struct {
 
 size_t climsr_sr_metrics_workspace(void);
 int climsr_sr_metrics(const ClimsrMetricsDesc* d, void* stream);
+/* The same results per image: out is [n][CLIMSR_SR_METRICS], row t = climsr_sr_metrics of the one-image batch {t} (its own
+ * min[t] / max[t], PSNR and SSIM ranges, R2 sums).  Three launches whatever n; fp64, fixed order, no atomics; row t is
+ * bit-identical for any n and any position of image t in the batch.  workspace: the helper's bytes (0 = bad sizes). */
+size_t climsr_sr_metrics_per_image_workspace(int n, int h, int w);
+int climsr_sr_metrics_per_image(const ClimsrMetricsDesc* d, void* stream);
 /* RegressionAccuracy.update: counts[0] += #(|p - t| <= eps) (float32), counts[1] += n.  int64 device counters. */
 int climsr_regression_accuracy_update(const float* preds, const float* target, int64_t n, float eps, int64_t* counts,
                                       void* stream);
