@@ -176,6 +176,7 @@ SIGNATURES = {
     "climsr_adaptive_pool_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                          c_void_p]),
     "climsr_adaptive_pool_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "climsr_adaptive_pool_kernel": (ctypes.c_char_p, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "climsr_linear_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int64,
                                   c_void_p, c_void_p]),
     "climsr_linear_dgrad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),

@@ -630,6 +630,23 @@ __global__ __launch_bounds__(256) void adaptive_pool_bwd_tile_kernel(const float
   }
 }
 
+// Route predicates, shared by the launchers and the dry-run query (climsr_adaptive_pool_kernel): the tiled kernels
+// need whole 64-channel blocks, the staged tile (input plane forward, pooled gradient backward) within LDS and the
+// window tables within AP_MAXD; the backward also at most AP_MAXC windows per input row / column (oh <= 2h) and
+// at least one input row per z-slice.
+static bool ap_fwd_tiled(int h, int w, int c, int oh, int ow) {
+  return c % AP_CB == 0 && ((size_t)h * w + 1) * AP_CB * 2 <= AP_LDS && oh <= AP_MAXD && ow <= AP_MAXD;
+}
+static bool ap_bwd_tiled(int h, int w, int c, int oh, int ow) {
+  return c % AP_CB == 0 && ((size_t)oh * ow + 1) * AP_CB * 4 <= AP_LDS && h <= AP_MAXD && w <= AP_MAXD && oh <= AP_MAXD &&
+         ow <= AP_MAXD && oh <= 2 * h && ow <= 2 * w && h >= AP_SPLIT;
+}
+
+extern "C" const char* climsr_adaptive_pool_kernel(int h, int w, int c, int oh, int ow, int bwd) {
+  if (bwd) return ap_bwd_tiled(h, w, c, oh, ow) ? "adaptive_pool_bwd_tile_kernel" : "adaptive_pool_bwd_kernel";
+  return ap_fwd_tiled(h, w, c, oh, ow) ? "adaptive_pool_fwd_tile_kernel" : "adaptive_pool_fwd_kernel";
+}
+
 extern "C" int climsr_adaptive_pool_fwd(const uint16_t* x, int n, int h, int w, int c, int oh, int ow, uint16_t* out,
                                         uint16_t* out_t, int n_pad, void* stream) {
   if (!x || !out || oh <= 0 || ow <= 0 || (out_t && n_pad < n)) {
@@ -637,7 +654,7 @@ extern "C" int climsr_adaptive_pool_fwd(const uint16_t* x, int n, int h, int w, 
     return CLIMSR_EINVAL;
   }
   hipStream_t st = (hipStream_t)stream;
-  if (c % AP_CB == 0 && ((size_t)h * w + 1) * AP_CB * 2 <= AP_LDS && oh <= AP_MAXD && ow <= AP_MAXD) {
+  if (ap_fwd_tiled(h, w, c, oh, ow)) {
     // one workgroup per (image, 64 channels): NHWC tile staged once, NCHW-flattened output written contiguously;
     // the [feat][n_pad] copy by a tiled transpose (both sides coalesced)
     hipLaunchKernelGGL(adaptive_pool_fwd_tile_kernel, dim3(c / AP_CB, n, AP_SPLIT), dim3(256), 0, st, x, h, w, c, oh, ow, out);
@@ -658,8 +675,7 @@ extern "C" int climsr_adaptive_pool_bwd(const float* dp, int n, int h, int w, in
     set_error("adaptive_pool_bwd: bad args");
     return CLIMSR_EINVAL;
   }
-  if (c % AP_CB == 0 && ((size_t)oh * ow + 1) * AP_CB * 4 <= AP_LDS && h <= AP_MAXD && w <= AP_MAXD && oh <= AP_MAXD &&
-      ow <= AP_MAXD && oh <= 2 * h && ow <= 2 * w && h >= AP_SPLIT) {
+  if (ap_bwd_tiled(h, w, c, oh, ow)) {
     hipLaunchKernelGGL(adaptive_pool_bwd_tile_kernel, dim3(c / AP_CB, n, AP_SPLIT), dim3(256), 0, (hipStream_t)stream, dp, h, w, c, oh,
                        ow, dx);
     return check_launch("adaptive_pool_bwd");

@@ -354,6 +354,10 @@ int climsr_adaptive_pool_fwd(const uint16_t* x, int n, int h, int w, int c, int 
 /* Backward: dx [n][h][w][c] fp32 (overwritten) from dp [n][c*oh*ow] fp32. */
 int climsr_adaptive_pool_bwd(const float* dp, int n, int h, int w, int c, int oh, int ow, float* dx, void* stream);
 
+/* Dry run of the two dispatches above: the name of the kernel climsr_adaptive_pool_fwd (bwd = 0) or
+ * climsr_adaptive_pool_bwd (bwd != 0) launches for this geometry (the tiled LDS kernel or the element-per-thread one). */
+const char* climsr_adaptive_pool_kernel(int h, int w, int c, int oh, int ow, int bwd);
+
 /* nn.Linear forward on MFMA: y[n][o] = act(x[n][k] . w[o][k] + b[o]) (fp32 out); n <= 64, k % 32 == 0,
  * o % 16 == 0; split-K partials in workspace (ws_floats >= nsplit*n*o, nsplit <= 3072/ceil(o/64) + 1). */
 int climsr_linear_fwd(const uint16_t* x, const uint16_t* w, const float* bias, int n, int k, int o, int act, float slope,

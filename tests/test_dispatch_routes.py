@@ -150,3 +150,20 @@ def test_weight_gradient_routes(routes):
     p2 = plan(128, 128, 3, 2, bias=False)
     p2.wgrad(bf(), 128, 0, 128, 128, bf(), 128, N, Workspace(), accumulate=False)
     assert _wgrad_name(routes) == "conv_wgrad64_kernel<1, 2>"
+
+
+@pytest.mark.parametrize("h,oh,want_fwd,want_bwd", [
+    (16, 14, "adaptive_pool_fwd_tile_kernel", "adaptive_pool_bwd_tile_kernel"),  # RFB discriminator: 16^2 -> 14^2, 512 ch
+    (4, 4, "adaptive_pool_fwd_tile_kernel", "adaptive_pool_bwd_tile_kernel"),    # plain discriminator: identity 4^2, 512 ch
+    (32, 14, "adaptive_pool_fwd_kernel", "adaptive_pool_bwd_tile_kernel"),       # input plane past the forward's LDS tile
+])
+def test_adaptive_pool_routes(h, oh, want_fwd, want_bwd):
+    """The discriminators' pools take the tiled kernels (climsr_adaptive_pool_kernel: the launchers' own predicates)."""
+    try:
+        lib = _lib.load()
+    except OSError as e:
+        pytest.skip(f"libclimsr_hip.so not loadable: {e}")
+    assert lib.climsr_adaptive_pool_kernel(h, h, 512, oh, oh, 0).decode() == want_fwd
+    assert lib.climsr_adaptive_pool_kernel(h, h, 512, oh, oh, 1).decode() == want_bwd
+    assert lib.climsr_adaptive_pool_kernel(h, h, 24, oh, oh, 0).decode() == "adaptive_pool_fwd_kernel"
+    assert lib.climsr_adaptive_pool_kernel(h, h, 24, oh, oh, 1).decode() == "adaptive_pool_bwd_kernel"
