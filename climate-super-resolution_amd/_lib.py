@@ -157,6 +157,10 @@ SIGNATURES = {
                                          c_void_p]),
     "climsr_adamw_step_scaled": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                          c_void_p, c_void_p]),
+    "climsr_opt_hparams": (c_int, [c_void_p, c_int] + [c_double] * 11 + [c_void_p, c_void_p]),
+    "climsr_adam_step": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "climsr_adam_step_scaled": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                        c_void_p, c_void_p]),
     "climsr_grad_norm_chunk": (c_int64, []),
     "climsr_grad_norm_workspace": (c_int64, [c_int64, c_int]),
     "climsr_grad_norm": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p,

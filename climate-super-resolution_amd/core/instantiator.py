@@ -8,6 +8,7 @@ conf/schedulers/one_cycle_schedule.yaml) need.
 from __future__ import annotations
 
 import importlib
+import types
 from typing import Any, Mapping
 
 import torch
@@ -44,32 +45,36 @@ class HydraInstantiator:
 
     def optimizer(self, model: torch.nn.Module, cfg):
         """instantiator.py:48-49.  For a native (flat-parameter) network ``torch.optim.AdamW`` resolves to the fused
-        ``climsr_amd.core.optim.AdamW`` (same hyper-parameters and param_groups, so OneCycleLR drives it unchanged);
-        any other optimizer is instantiated as configured and re-packs the network's bf16 MFMA weights after each
+        ``climsr_amd.core.optim.AdamW`` (same hyper-parameters and param_groups, so OneCycleLR drives it unchanged)
+        and ``torch.optim.Adam`` to the fused ``climsr_amd.core.optim.Adam``; with an option the fused update lacks
+        (amsgrad, maximize, ...) either falls back to torch's class.  Any other optimizer is instantiated as configured and re-packs the network's bf16 MFMA weights after each
         step (the kernels read those, not the fp32 masters)."""
         cfg = dict(cfg)
         native = hasattr(model, "_flat") and hasattr(model, "repack_weights")
-        if native and cfg.get("_target_") in ("torch.optim.AdamW", "climsr_amd.core.optim.AdamW"):
-            from .optim import AdamW
+        fused = {"torch.optim.AdamW": "AdamW", "climsr_amd.core.optim.AdamW": "AdamW",
+                 "torch.optim.Adam": "Adam", "climsr_amd.core.optim.Adam": "Adam"}.get(cfg.get("_target_"))
+        if native and fused is not None:
+            from . import optim
 
+            cls = getattr(optim, fused)
             params = {k: v for k, v in cfg.items() if not k.startswith("_")}
-            unsupported = dict(AdamW._UNSUPPORTED, amsgrad=False)
+            unsupported = dict(cls._UNSUPPORTED, amsgrad=False)
             odd = {k: v for k, v in params.items() if k in unsupported and v != unsupported[k]}
             if not odd:
-                return AdamW(model.parameters(), owner=model, **params)
-            # options the fused update does not implement (amsgrad, maximize, foreach, ...): torch's own AdamW + repack
-            opt = torch.optim.AdamW(model.parameters(), **params)
+                return cls(model.parameters(), owner=model, **params)
+            # options the fused update does not implement (amsgrad, maximize, foreach, ...): torch's own class + repack
+            opt = getattr(torch.optim, fused)(model.parameters(), **params)
         else:
             opt = self.instantiate(cfg, model.parameters())
         if native:
             step = opt.step
 
-            def step_and_repack(*a, **kw):
+            def step_and_repack(_opt, *a, **kw):
                 out = step(*a, **kw)
                 model.repack_weights()
                 return out
 
-            opt.step = step_and_repack
+            opt.step = types.MethodType(step_and_repack, opt)  # a bound method: torch's schedulers wrap step.__func__
         return opt
 
     def scheduler(self, cfg, optimizer):

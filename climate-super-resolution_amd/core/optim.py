@@ -4,6 +4,10 @@ Replaces ``torch.optim.AdamW`` (conf/optimizers/adamw.yaml: lr, weight_decay=1e-
 (0.9,0.999) with beta1 cycled by OneCycleLR, eps 1e-8) wired by
 ``climsr/core/instantiator.py:48-49`` and ``OneCycleLR`` (conf/schedulers/one_cycle_schedule.yaml,
 instantiator.py:51-64).  One kernel updates a whole network's flat fp32 buffer.
+
+``Adam`` is the same for ``torch.optim.Adam`` (conf/optimizers/adam.yaml: coupled L2 weight decay), and ``DeviceStepped``
+turns an eager (``AdamW`` | ``Adam``, scheduler or None) pair into the form a captured step replays: counters, schedule
+(OneCycleLR, none, or one of five transformers warm-up lambdas: ``climsr_opt_hparams``) and update all on the device.
 """
 from __future__ import annotations
 
@@ -144,6 +148,7 @@ class AdamW(torch.optim.Optimizer):
 
     # torch.optim.AdamW options this fused update does not implement: accepted only at their default value
     _UNSUPPORTED = {"maximize": False, "foreach": None, "fused": None, "capturable": False, "differentiable": False}
+    _COUPLED = False  # True (Adam): the weight decay is an L2 term added to the gradient, not a decay of the weights
 
     def __init__(self, params: Iterable, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  amsgrad: bool = False, owner=None, **kwargs):
@@ -151,9 +156,9 @@ class AdamW(torch.optim.Optimizer):
             raise ValueError("amsgrad is not supported")
         for k, v in kwargs.items():
             if k not in self._UNSUPPORTED:
-                raise TypeError(f"AdamW got an unexpected keyword argument {k!r}")
+                raise TypeError(f"{type(self).__name__} got an unexpected keyword argument {k!r}")
             if v != self._UNSUPPORTED[k]:
-                raise ValueError(f"AdamW option {k}={v!r} is not supported by the fused update (only {self._UNSUPPORTED[k]!r})")
+                raise ValueError(f"{type(self).__name__} option {k}={v!r} is not supported by the fused update (only {self._UNSUPPORTED[k]!r})")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.owner = owner
         self._hp = None
@@ -170,15 +175,15 @@ class AdamW(torch.optim.Optimizer):
                 continue
             flat = _flat_owner(group["params"])
             if flat is None:
-                raise ValueError(f"AdamW.load_state_dict: group {gi} carries flat-buffer moments but its parameters are "
+                raise ValueError(f"{type(self).__name__}.load_state_dict: group {gi} carries flat-buffer moments but its parameters are "
                                  "not the views of one flat buffer")
             if not isinstance(st.get("step"), int) or st["step"] < 1:
-                raise ValueError(f"AdamW.load_state_dict: group {gi} has moments but step={st.get('step')!r}")
+                raise ValueError(f"{type(self).__name__}.load_state_dict: group {gi} has moments but step={st.get('step')!r}")
             for k in ("m", "v"):
                 t = st.get(k)
                 if not isinstance(t, torch.Tensor) or t.shape != flat.shape or t.dtype != flat.dtype or not t.is_contiguous():
                     got = f"{tuple(t.shape)} {t.dtype} contiguous={t.is_contiguous()}" if isinstance(t, torch.Tensor) else repr(t)
-                    raise ValueError(f"AdamW.load_state_dict: group {gi} moment {k!r} is {got}; the flat parameter buffer "
+                    raise ValueError(f"{type(self).__name__}.load_state_dict: group {gi} moment {k!r} is {got}; the flat parameter buffer "
                                      f"is {tuple(flat.shape)} {flat.dtype}")
                 st[k] = t.to(flat.device, copy=True)  # never the caller's tensor: the update writes it in place
 
@@ -218,7 +223,7 @@ class AdamW(torch.optim.Optimizer):
                 if "m" not in st:
                     st["m"] = torch.zeros_like(flat)
                     st["v"] = torch.zeros_like(flat)
-                _adamw_flat(lib, self.owner, flat, gflat, st["m"], st["v"], hp, _lib.stream_ptr(), grad_scale)
+                _adamw_flat(lib, self.owner, flat, gflat, st["m"], st["v"], hp, _lib.stream_ptr(), grad_scale, self._COUPLED)
                 mirrored = True
             else:
                 for p in params:
@@ -231,6 +236,10 @@ class AdamW(torch.optim.Optimizer):
                         g = g.clone() if g.data_ptr() == p.grad.data_ptr() else g  # .grad stays unclipped
                         _launch("grad_scale", lambda: lib.climsr_scale_f32(ptr(g), g.numel(), ptr(grad_scale), _lib.stream_ptr()),
                                 nbytes=8 * g.numel())
+                    if self._COUPLED:
+                        _launch("adam", lambda: lib.climsr_adam_step(p.numel(), ptr(p), ptr(g), ptr(ps["m"]), ptr(ps["v"]), ptr(hp),
+                                                                     0, 0, None, _lib.stream_ptr()), nbytes=28 * p.numel())
+                        continue
                     _launch("adamw", lambda: lib.climsr_adamw_step(p.numel(), ptr(p), ptr(g), ptr(ps["m"]), ptr(ps["v"]), ptr(hp),
                                                                    _lib.stream_ptr()), nbytes=28 * p.numel())
         if self.owner is not None:
@@ -247,10 +256,21 @@ def _mirror_of(module):
     return fn() if fn is not None else None
 
 
-def _adamw_flat(lib, module, flat, gflat, m, v, hp, stream, grad_scale=None):
+def _adamw_flat(lib, module, flat, gflat, m, v, hp, stream, grad_scale=None, coupled=False):
     """One fused AdamW launch over a flat buffer; when ``module`` mirrors part of it in bf16 (``bf16_mirror()``), the
-    same pass writes that copy.  ``grad_scale`` (device scalar): the update reads gradient * grad_scale."""
+    same pass writes that copy.  ``grad_scale`` (device scalar): the update reads gradient * grad_scale.  ``coupled``:
+    the Adam update (L2 term in the gradient) instead."""
     mir = _mirror_of(module) if module is not None else None
+    if coupled:
+        lo, n, buf = mir if mir is not None else (0, 0, None)
+        if grad_scale is not None:
+            _launch("adam_scaled", lambda: lib.climsr_adam_step_scaled(flat.numel(), ptr(flat), ptr(gflat), ptr(m), ptr(v), ptr(hp),
+                                                                       ptr(grad_scale), lo, n, ptr(buf), stream),
+                    nbytes=28 * flat.numel() + 2 * n)
+        else:
+            _launch("adam", lambda: lib.climsr_adam_step(flat.numel(), ptr(flat), ptr(gflat), ptr(m), ptr(v), ptr(hp), lo, n,
+                                                         ptr(buf), stream), nbytes=28 * flat.numel() + 2 * n)
+        return
     if grad_scale is not None:
         lo, n, buf = mir if mir is not None else (0, 0, None)
         _launch("adamw_scaled", lambda: lib.climsr_adamw_step_scaled(flat.numel(), ptr(flat), ptr(gflat), ptr(m), ptr(v), ptr(hp),
@@ -307,3 +327,232 @@ class GraphedAdamW:
             self.module.engine().repack(mirror_done=True)
         else:
             self.module.engine().repack()
+
+
+class Adam(AdamW):
+    """Drop-in for torch.optim.Adam (amsgrad=False; conf/optimizers/adam.yaml: coupled L2 ``weight_decay``) whose update
+    runs in libclimsr_hip (``climsr_adam_step`` / ``climsr_adam_step_scaled``).  Everything else is ``AdamW``'s:
+    ``param_groups`` read at every step, flat m / v in ``state["group%d"]``, ``step(grad_scale=)``, the re-pack."""
+
+    _COUPLED = True
+
+    def __init__(self, params: Iterable, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 amsgrad: bool = False, owner=None, **kwargs):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, owner=owner, **kwargs)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Schedules the device can step (climsr_opt_hparams), restated in float64 Python.  ``lr_lambda`` is transformers' own
+# formula per kind; ``onecycle_lr_beta1`` is torch's OneCycleLR (cos annealing, two phases, beta1 cycled).
+# ---------------------------------------------------------------------------------------------------------------------
+SCHED_ONECYCLE, SCHED_NONE, SCHED_CONSTANT, SCHED_CONSTANT_WARMUP, SCHED_LINEAR_WARMUP, SCHED_COSINE_WARMUP, \
+    SCHED_COSINE_RESTARTS_WARMUP = range(7)
+
+_TRANSFORMERS_LAMBDAS = {  # the lambda's function name (transformers >= 4.30) / its factory's name (older closures)
+    "_get_constant_lambda": SCHED_CONSTANT, "get_constant_schedule": SCHED_CONSTANT,
+    "_get_constant_schedule_with_warmup_lr_lambda": SCHED_CONSTANT_WARMUP, "get_constant_schedule_with_warmup": SCHED_CONSTANT_WARMUP,
+    "_get_linear_schedule_with_warmup_lr_lambda": SCHED_LINEAR_WARMUP, "get_linear_schedule_with_warmup": SCHED_LINEAR_WARMUP,
+    "_get_cosine_schedule_with_warmup_lr_lambda": SCHED_COSINE_WARMUP, "get_cosine_schedule_with_warmup": SCHED_COSINE_WARMUP,
+    "_get_cosine_with_hard_restarts_schedule_with_warmup_lr_lambda": SCHED_COSINE_RESTARTS_WARMUP,
+    "get_cosine_with_hard_restarts_schedule_with_warmup": SCHED_COSINE_RESTARTS_WARMUP,
+}
+
+
+def lr_lambda(kind: int, step: int, warmup: float = 0.0, total: float = 0.0, cycles: float = 0.5) -> float:
+    """lambda(step) of a ``SCHED_*`` kind other than OneCycleLR, in float64, as transformers/optimization.py writes it
+    (``warmup`` may be fractional: the host lambdas use the task's un-rounded warm-up product as it is)."""
+    import math
+
+    if kind in (SCHED_NONE, SCHED_CONSTANT):
+        return 1.0
+    if step < warmup:
+        return float(step) / float(max(1.0, warmup))
+    if kind == SCHED_CONSTANT_WARMUP:
+        return 1.0
+    if kind == SCHED_LINEAR_WARMUP:
+        return max(0.0, float(total - step) / float(max(1.0, total - warmup)))
+    progress = float(step - warmup) / float(max(1.0, total - warmup))
+    if kind == SCHED_COSINE_WARMUP:
+        return max(0.0, 0.5 * (1.0 + math.cos(math.pi * float(cycles) * 2.0 * progress)))
+    if kind == SCHED_COSINE_RESTARTS_WARMUP:
+        if progress >= 1.0:
+            return 0.0
+        return max(0.0, 0.5 * (1.0 + math.cos(math.pi * ((float(cycles) * progress) % 1.0))))
+    raise ValueError(f"lr_lambda: unknown schedule kind {kind!r}")
+
+
+def onecycle_lr_beta1(step: int, total_steps: int, max_lr: float, pct_start: float, div_factor: float, final_div_factor: float,
+                      base_momentum: float = 0.85, max_momentum: float = 0.95):
+    """(lr, beta1) of torch's OneCycleLR at ``last_epoch == step`` (anneal_strategy "cos", three_phase False)."""
+    import math
+
+    def cos_anneal(start, end, pct):
+        return end + (start - end) / 2.0 * (math.cos(math.pi * pct) + 1)
+
+    initial_lr = max_lr / div_factor
+    min_lr = initial_lr / final_div_factor
+    end0, end1 = float(pct_start * total_steps) - 1, total_steps - 1
+    if step <= end0:
+        pct = step / end0
+        return cos_anneal(initial_lr, max_lr, pct), cos_anneal(max_momentum, base_momentum, pct)
+    pct = (step - end0) / (end1 - end0)
+    return cos_anneal(max_lr, min_lr, pct), cos_anneal(base_momentum, max_momentum, pct)
+
+
+def _solve(fn, want: float, guess: float) -> Optional[float]:
+    """A float x near ``guess`` with fn(x) == want exactly (the scheduler keeps fn's value, the kernel wants x)."""
+    import math
+
+    cands = [float(f"{guess:.12g}"), guess]  # the short decimal the user most likely wrote, first
+    lo = hi = guess
+    for _ in range(4):
+        lo, hi = math.nextafter(lo, -math.inf), math.nextafter(hi, math.inf)
+        cands += [lo, hi]
+    for x in cands:
+        if fn(x) == want:
+            return x
+    return None
+
+
+def _describe_schedule(optimizer, scheduler):
+    """(kind, dict of climsr_opt_hparams' schedule scalars) of a scheduler the device can step, else NotImplementedError."""
+    pair = f"({type(optimizer).__name__}, {type(scheduler).__name__ if scheduler is not None else None})"
+    if scheduler is None:
+        return SCHED_NONE, {}
+    if getattr(scheduler, "optimizer", None) is not optimizer:
+        raise NotImplementedError(f"the pair {pair} cannot be stepped on the device: the scheduler drives another optimizer")
+    group = optimizer.param_groups[0]
+    if isinstance(scheduler, torch.optim.lr_scheduler.OneCycleLR):
+        anneal = getattr(scheduler, "_anneal_func_type", None) or \
+            {"_annealing_cos": "cos", "_annealing_linear": "linear"}.get(getattr(scheduler._anneal_func, "__name__", ""), "?")
+        odd = []
+        if anneal != "cos":
+            odd.append(f"anneal_strategy={anneal!r}")
+        if len(scheduler._schedule_phases) != 2:
+            odd.append("three_phase=True")
+        if not (scheduler.cycle_momentum and getattr(scheduler, "use_beta1", False)):
+            odd.append("cycle_momentum=False")
+        elif (group["base_momentum"], group["max_momentum"]) != (0.85, 0.95):
+            odd.append(f"base_momentum={group['base_momentum']!r}, max_momentum={group['max_momentum']!r}")
+        if odd:
+            raise NotImplementedError(f"the pair {pair} cannot be stepped on the device: OneCycleLR with {', '.join(odd)} "
+                                      "(only cos annealing in two phases with beta1 cycled 0.95 <-> 0.85)")
+        total, max_lr = int(scheduler.total_steps), float(group["max_lr"])
+        end0 = scheduler._schedule_phases[0]["end_step"]
+        pct = _solve(lambda x: float(x * total) - 1, end0, (end0 + 1) / total)
+        div = _solve(lambda x: max_lr / x, group["initial_lr"], max_lr / group["initial_lr"])
+        fdiv = None if div is None else _solve(lambda x: max_lr / div / x, group["min_lr"], group["initial_lr"] / group["min_lr"])
+        if pct is None or div is None or fdiv is None:
+            raise NotImplementedError(f"the pair {pair} cannot be stepped on the device: OneCycleLR's pct_start, div_factor "
+                                      "or final_div_factor could not be recovered from the scheduler exactly")
+        return SCHED_ONECYCLE, dict(lr=max_lr, total=float(total), pct_start=pct, div_factor=div, final_div_factor=fdiv)
+    if isinstance(scheduler, torch.optim.lr_scheduler.LambdaLR) and len(scheduler.lr_lambdas) == 1:
+        fn = scheduler.lr_lambdas[0]
+        inner = getattr(fn, "func", fn)
+        kw = dict(getattr(fn, "keywords", None) or {})
+        if getattr(inner, "__closure__", None):  # older transformers: a closure over the factory's arguments
+            kw.update({k: c.cell_contents for k, c in zip(inner.__code__.co_freevars, inner.__closure__)})
+        name = getattr(inner, "__qualname__", "").split(".<locals>")[0]
+        kind = _TRANSFORMERS_LAMBDAS.get(name) if str(getattr(inner, "__module__", "")).startswith("transformers") else None
+        if kind is not None and not kw.get("min_lr_rate"):
+            sc = dict(warmup=float(kw.get("num_warmup_steps", 0.0)), total=float(kw.get("num_training_steps", 0.0)),
+                      cycles=float(kw.get("num_cycles", 0.5)))
+            probe = sorted({0, 1, int(sc["warmup"]), int(sc["warmup"]) + 1, int(sc["total"]) // 2, max(0, int(sc["total"]) - 1)})
+            if sc["warmup"] >= 0.0 and all(abs(fn(s) - lr_lambda(kind, s, **sc)) <= 1e-15 for s in probe):
+                return kind, dict(sc, lr=float(scheduler.base_lrs[0]))
+    raise NotImplementedError(f"the pair {pair} cannot be stepped on the device: only no scheduler, OneCycleLR and transformers' "
+                              "constant, constant / linear / cosine / cosine-with-hard-restarts warm-up schedules are "
+                              "implemented (the polynomial schedule stays on the eager path)")
+
+
+class DeviceStepped:
+    """The device-stepped form of an eager ``(optimizer, scheduler or None)`` pair, for captured training steps:
+    ``GraphedAdamW`` generalised to ``core.optim.AdamW`` / ``Adam`` and every schedule ``climsr_opt_hparams`` knows.
+
+    ``step()`` launches the schedule kernel (lr, betas and bias corrections from the device counters, which it
+    increments), with ``max_grad_norm`` the L2 norm of the flat gradient, the fused update (reading the device clip
+    coefficient) and the bf16 re-pack; it returns that coefficient (or None).  m and v are the eager optimizer's own
+    tensors, the counters start from its ``state["group0"]["step"]`` and the scheduler's ``last_epoch``, and ``flush()``
+    writes them back to the host objects with one host read, after which those are what the eager pair would be.
+    A pair it cannot express raises ``NotImplementedError`` naming the pair."""
+
+    def __init__(self, optimizer, scheduler=None, max_grad_norm: Optional[float] = None):
+        pair = f"({type(optimizer).__name__}, {type(scheduler).__name__ if scheduler is not None else None})"
+        if type(optimizer) not in (AdamW, Adam):
+            raise NotImplementedError(f"the pair {pair} cannot be stepped on the device: only climsr_amd.core.optim.AdamW and "
+                                      "Adam (the fused updates over a flat parameter buffer) are implemented")
+        module = optimizer.owner
+        if len(optimizer.param_groups) != 1 or module is None or getattr(module, "_flat", None) is None or \
+                [id(p) for p in optimizer.param_groups[0]["params"]] != [id(p) for p, _o, _n in module._flat_index]:
+            raise NotImplementedError(f"the pair {pair} cannot be stepped on the device: the optimizer must hold the "
+                                      "parameters of one native flat-parameter network in one group")
+        self.kind, self.sched_cfg = _describe_schedule(optimizer, scheduler)
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError(f"max_grad_norm must be positive, got {max_grad_norm!r}")
+        self.optimizer, self.scheduler, self.module, self.max_grad_norm = optimizer, scheduler, module, max_grad_norm
+        self.coupled = optimizer._COUPLED
+        flat = module._flat
+        st = optimizer.state.setdefault("group0", {})
+        if "m" not in st:
+            st["m"], st["v"] = torch.zeros_like(flat), torch.zeros_like(flat)
+        self.m, self.v = st["m"], st["v"]
+        last_epoch = scheduler.last_epoch if scheduler is not None else 0
+        self.state = torch.tensor([float(st.get("step", 0)), float(last_epoch)], dtype=torch.float64).to(flat.device)
+        self.hp = torch.zeros(8, dtype=torch.float32, device=flat.device)
+        self.grad_norm = None
+        if max_grad_norm is not None:
+            self.grad_norm = GradNorm.of(module)
+            if flat.is_cuda:
+                self.grad_norm._prepare(_lib.load())  # offsets table and workspace now: step() may run inside a capture
+
+    def zero_grad(self, set_to_none: bool = True) -> None:
+        self.optimizer.zero_grad(set_to_none=set_to_none)
+
+    def step(self):
+        lib = _lib.load()
+        s = _lib.stream_ptr()
+        group, c = self.optimizer.param_groups[0], self.sched_cfg
+        b1, b2 = group["betas"]
+        lr = c.get("lr", group["lr"])  # a scheduler's base / max lr; without one the group's current lr
+        _launch("opt_hparams", lambda: lib.climsr_opt_hparams(
+            ptr(self.state), self.kind, float(lr), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+            c.get("warmup", 0.0), c.get("total", 0.0), c.get("cycles", 0.0), c.get("pct_start", 0.0), c.get("div_factor", 0.0),
+            c.get("final_div_factor", 0.0), ptr(self.hp), s))
+        module = self.module
+        flat = module._flat
+        if flat.numel() != self.m.numel() or flat.device != self.m.device:
+            raise RuntimeError("DeviceStepped: the network's flat parameter buffer changed size or device; build the "
+                               "optimizers again")
+        gflat = _gather_flat_grad(module, flat, group["params"])
+        if gflat is None:
+            raise RuntimeError("DeviceStepped.step: a parameter has no gradient in the network's flat gradient buffer")
+        coef = None
+        if self.grad_norm is not None:
+            coef = self.grad_norm(2, self.max_grad_norm, gathered=gflat.data_ptr() == module._flat_grad.data_ptr())[2]
+        _adamw_flat(lib, module, flat, gflat, self.m, self.v, self.hp, s, coef, self.coupled)
+        if _mirror_of(module) is not None:
+            module.engine().repack(mirror_done=True)
+        else:
+            module.engine().repack()
+        return coef
+
+    def flush(self) -> None:
+        """The device counters into the host objects (one host read): the optimizer's step count, the scheduler's
+        ``last_epoch`` / ``_step_count`` / ``_last_lr`` and ``param_groups[0]["lr"]`` / ``"betas"`` -- through the
+        scheduler's own ``get_lr()``, so they are what its ``step()`` would have left."""
+        step, last_epoch = (int(x) for x in self.state.tolist())
+        st = self.optimizer.state["group0"]
+        st["step"] = step
+        st["m"], st["v"] = self.m, self.v
+        if step == 0:  # nothing stepped yet: a state without moments, as the eager optimizer's
+            del st["m"], st["v"], st["step"]
+        sch = self.scheduler
+        if sch is None or sch.last_epoch == last_epoch:
+            return
+        sch.last_epoch = last_epoch
+        sch._step_count = last_epoch + 1
+        with torch.optim.lr_scheduler._enable_get_lr_call(sch):
+            values = sch.get_lr()  # OneCycleLR also writes betas[0] here
+        for group, lr in zip(self.optimizer.param_groups, values):
+            group["lr"] = lr
+        sch._last_lr = [group["lr"] for group in self.optimizer.param_groups]

@@ -41,6 +41,20 @@ Epochs, validation, test and resume (all off by default; ``fit(batches)`` stays 
 - ``callbacks=[ModelCheckpoint(...), EarlyStopping(...)]`` run after each validation inside ``fit`` (one host read of the
   monitored value each).  ``resume_from_checkpoint=path`` restores weights, optimizer and scheduler states, ``epoch`` and
   ``global_step`` and continues with the next epoch, bit-identical to the uninterrupted run.
+
+``graph_steps=True`` (off by default; ``graph_warmup=2``): every optimizer / scheduler pair becomes its device-stepped
+form (core/optim.DeviceStepped) at construction, after a resume.  The first ``graph_warmup`` batches run that step
+eagerly on a side stream; then the batch's whole step -- every optimizer's zero_grad, training_step, backward and device
+step, with the toggling -- is captured once, on one stream, into a private graph pool, and every later batch with the same
+tensor shapes and dtypes is copied into static inputs and replayed.  Before each replay the host checks the capture's
+key: the batch signature, and per network the flat buffer's pointer, the engine object and the re-pack rule's version
+key.  Another signature (an epoch's short last batch) runs one eager device-stepped step and leaves the capture alone; a
+moved pointer, engine or version (``load_state_dict``, ``p.mul_()``, ``.to()``) drops it, one eager step re-packs, and
+the step is captured again.  ``training_batch`` returns copies of the losses; ``module.logged`` holds the capture's own
+output tensors.  The step counts and ``last_epoch`` live on the device and are flushed to the optimizers and schedulers
+before ``save_checkpoint``, the callbacks after a validation and the end of ``fit``.  ``accumulate_grad_batches > 1``,
+``track_grad_norm``, ``terminate_on_nan``, a DDP-wrapped network, a grad-ready hook and a pair the device cannot step
+are refused at construction.  ``graph_stats`` counts captures, replayed and eager steps.
 """
 from __future__ import annotations
 
@@ -173,6 +187,27 @@ class EarlyStopping:
             trainer.should_stop, self.stopped_epoch = True, trainer.current_epoch
 
 
+def _reachable_tensors(roots) -> List[Any]:
+    """Every tensor reachable from ``roots`` through containers, nn.Modules and this package's own objects."""
+    import torch
+
+    seen, found, todo = set(), [], list(roots)
+    while todo:
+        x = todo.pop()
+        if id(x) in seen:
+            continue
+        seen.add(id(x))
+        if isinstance(x, torch.Tensor):
+            found.append(x)
+        elif isinstance(x, dict):
+            todo.extend(x.values())
+        elif isinstance(x, (list, tuple, set)):
+            todo.extend(x)
+        elif isinstance(x, torch.nn.Module) or type(x).__module__.split(".")[0] == __name__.split(".")[0]:
+            todo.extend(getattr(x, "__dict__", {}).values())
+    return found
+
+
 def _norm_label(track_grad_norm) -> Optional[str]:
     """Lightning's ``track_grad_norm`` value as the ``{p}`` of its log keys ("2.0" / "inf"), None for off (-1)."""
     t = track_grad_norm
@@ -200,7 +235,7 @@ class Trainer:
                  num_processes: int = 1, gradient_clip_val: float = 0.0, gradient_clip_algorithm: str = "norm",
                  track_grad_norm=-1, terminate_on_nan: bool = False, check_val_every_n_epoch: int = 1, limit_val_batches=1.0,
                  limit_test_batches=1.0, num_sanity_val_steps: int = 0, val_check_interval=1.0, callbacks=None,
-                 resume_from_checkpoint: Optional[str] = None):
+                 resume_from_checkpoint: Optional[str] = None, graph_steps: bool = False, graph_warmup: int = 2):
         if isinstance(accumulate_grad_batches, (dict, list, tuple)):
             raise NotImplementedError("accumulate_grad_batches: Lightning's per-epoch schedules (dict / list) are not "
                                       "implemented; pass one int >= 1")
@@ -240,6 +275,188 @@ class Trainer:
         self._set_progress(0, 0)
         if resume_from_checkpoint is not None:
             self._resume(resume_from_checkpoint)
+        self.graph_steps, self.graph_warmup = bool(graph_steps), graph_warmup
+        self.graph_stats = {"captures": 0, "replayed": 0, "eager": 0}
+        self._device_opts: List[Any] = []
+        self._capture = None  # (key, graph, static batch tensors, static outputs, entries of module.logged)
+        self._graph_streams = None
+        self._graph_seen, self._graph_sig = 0, None  # eager steps taken towards the capture, and the batch signature it is for
+        if self.graph_steps:
+            self._init_graph_steps()
+
+    # -- graph mode: device-stepped optimizers, one captured step per batch signature
+    def _init_graph_steps(self) -> None:
+        """The refusals of ``graph_steps=True`` (nothing it cannot capture is silently run eagerly), then every
+        optimizer / scheduler pair into its device-stepped form (core/optim.DeviceStepped)."""
+        if isinstance(self.graph_warmup, bool) or not isinstance(self.graph_warmup, int) or self.graph_warmup < 1:
+            raise ValueError(f"graph_warmup must be an int >= 1 (the eager steps before the capture make the engines' "
+                             f"lazy allocations), got {self.graph_warmup!r}")
+        if self.accumulate_grad_batches > 1:
+            raise NotImplementedError(f"graph_steps=True does not support accumulate_grad_batches={self.accumulate_grad_batches} "
+                                      "(an accumulation window inside a capture is not implemented); use 1")
+        if self._norm_label is not None:
+            raise NotImplementedError(f"graph_steps=True does not support track_grad_norm={self.track_grad_norm!r} "
+                                      "(per-parameter norm logging is not captured); use -1")
+        if self.terminate_on_nan:
+            raise NotImplementedError("graph_steps=True does not support terminate_on_nan=True (it reads the loss on the "
+                                      "host before every update)")
+        for name, net in zip(NET_NAMES, self.nets):
+            if any(c.__name__ == "DistributedDataParallel" for c in type(net).__mro__):
+                raise NotImplementedError(f"graph_steps=True does not support a {name} wrapped in torch "
+                                          "DistributedDataParallel (multi-rank capture is bench.py's)")
+            if getattr(net, "_grad_ready_hook", None) is not None:
+                raise NotImplementedError(f"graph_steps=True does not support a grad-ready hook on the {name} "
+                                          "(set_grad_ready_hook: multi-rank capture is bench.py's)")
+        if len(self.optimizers) != len(self.nets):
+            raise NotImplementedError(f"graph_steps=True needs one optimizer per network, got {len(self.optimizers)} for "
+                                      f"{len(self.nets)}")
+        from .optim import DeviceStepped
+
+        scheds = [s["scheduler"] if isinstance(s, dict) else s for s in self.schedulers]
+        used = set()
+        for i, opt in enumerate(self.optimizers):
+            mine = [s for s in scheds if getattr(s, "optimizer", None) is opt]
+            if len(mine) > 1:
+                raise NotImplementedError(f"graph_steps=True: optimizer {i} has {len(mine)} schedulers; one at most")
+            used.update(id(s) for s in mine)
+            try:
+                dev = DeviceStepped(opt, mine[0] if mine else None, max_grad_norm=self.gradient_clip_val or None)
+            except NotImplementedError as e:
+                raise NotImplementedError(f"graph_steps=True: optimizer {i}: {e}") from None
+            if dev.module is not self.nets[i]:
+                raise NotImplementedError(f"graph_steps=True: optimizer {i} does not own the {NET_NAMES[i]}'s parameters")
+            self._device_opts.append(dev)
+        if len(used) != len(scheds):
+            raise NotImplementedError("graph_steps=True: a scheduler drives an optimizer that is not one of the trainer's")
+
+    def flush_graph_state(self) -> None:
+        """Graph mode keeps the step counts and ``last_epoch`` on the device; this writes them back to the optimizers
+        and schedulers (one host read each).  Called before anything reads those: ``save_checkpoint``, the callbacks
+        after a validation, the end of ``fit``."""
+        for dev in self._device_opts:
+            dev.flush()
+
+    def _graph_key(self, batch):
+        sig = tuple((k, tuple(v.shape), v.dtype) for k, v in batch.items() if hasattr(v, "data_ptr"))
+        nets = tuple((net._flat.data_ptr(), id(net.engine())) + tuple(net.engine()._params_version()) for net in self.nets)
+        return sig, nets
+
+    def _graph_body(self, batch, batch_idx: int) -> List[Any]:
+        """The Trainer's step with the device-stepped optimizers: the launches of a warm-up step, of an eager step of
+        another batch signature, and of the capture."""
+        outs = []
+        nopt = len(self._device_opts)
+        for i, dev in enumerate(self._device_opts):
+            self._graph_opt = i
+            if nopt > 1:
+                self._toggle(i)
+            dev.zero_grad(set_to_none=True)
+            out = self.module.training_step(batch, batch_idx, i) if nopt > 1 else self.module.training_step(batch, batch_idx)
+            loss = out["loss"] if isinstance(out, dict) else out
+            loss.backward()
+            coef = dev.step()
+            if coef is not None:
+                self.module.log(f"grad_clip_coef/{NET_NAMES[i]}", coef.clone())
+            outs.append(out)
+        if nopt > 1:
+            for net in self.nets:
+                for p in net.parameters():
+                    p.requires_grad_(True)
+        return outs
+
+    @staticmethod
+    def _copies(x, clone: bool = True):
+        """``x`` with every tensor in it detached and, with ``clone``, copied (it stays valid after the next replay)."""
+        if hasattr(x, "data_ptr"):
+            return x.detach().clone() if clone else x.detach()
+        if isinstance(x, dict):
+            return {k: Trainer._copies(v, clone) for k, v in x.items()}
+        if isinstance(x, (list, tuple)):
+            return type(x)(Trainer._copies(v, clone) for v in x)
+        return x
+
+    def _graph_eager(self, batch, batch_idx: int, side: bool) -> List[Any]:
+        import torch
+
+        self.graph_stats["eager"] += 1
+        if not side:
+            return self._copies(self._graph_body(batch, batch_idx))
+        if self._graph_streams is None:
+            self._graph_streams = (torch.cuda.Stream(), torch.cuda.Stream())
+        s = self._graph_streams[0]
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            outs = self._copies(self._graph_body(batch, batch_idx))
+        torch.cuda.current_stream().wait_stream(s)
+        return outs
+
+    def _graph_capture(self, batch, batch_idx: int, key) -> None:
+        """Capture this batch's step into ``self._capture`` (nothing runs: the replay that follows is the step)."""
+        import torch
+
+        static = {k: (torch.empty_like(v) if hasattr(v, "data_ptr") else v) for k, v in batch.items()}
+        for k, v in batch.items():
+            if hasattr(v, "data_ptr"):
+                static[k].copy_(v)
+        pool = torch.cuda.graph_pool_handle()  # private, and new for every capture: a dropped capture takes its pool along
+        cap = self._graph_streams[1]
+        logged = getattr(self.module, "logged", None)
+        before = dict(logged) if logged is not None else {}
+        graph = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize()
+        cap.wait_stream(torch.cuda.current_stream())
+        self._graph_opt = 0
+        with torch.cuda.stream(cap):
+            # "relaxed": the backward's launches come from the autograd thread
+            graph.capture_begin(pool=pool, capture_error_mode="relaxed")
+            try:
+                outs = self._graph_body(static, batch_idx)
+            except BaseException as e:
+                try:
+                    graph.capture_end()  # never leave the stream capturing
+                except Exception:
+                    pass
+                for net in self.nets:  # the aborted step may have left one network frozen
+                    for p in net.parameters():
+                        p.requires_grad_(True)
+                raise RuntimeError(f"graph_steps=True: the step of optimizer {self._graph_opt} ({NET_NAMES[self._graph_opt]}) "
+                                   f"could not be captured: {type(e).__name__}: {e}") from e
+            graph.capture_end()
+        torch.cuda.current_stream().wait_stream(cap)
+        slogged = {k: v for k, v in logged.items() if before.get(k) is not v} if logged is not None else {}
+        outs = self._copies(outs, clone=False)  # the capture's own output tensors, without the autograd graph
+        # the capture reads and writes the engines' scratch tensors by address: hold every tensor reachable from the task
+        # now, so a step of another batch shape that re-allocates a scratch buffer cannot free one the replay still uses
+        self._capture = (key, graph, static, outs, slogged, _reachable_tensors([self.module, self._device_opts]))
+        self.graph_stats["captures"] += 1
+
+    def _graph_batch(self, batch: Dict[str, Any], batch_idx: int) -> List[Any]:
+        key = self._graph_key(batch)
+        cap = self._capture
+        if cap is not None and cap[0][1] != key[1]:  # a pointer, an engine or a version key moved: the capture is stale
+            cap = self._capture = None
+            # one eager step (it re-packs and re-allocates), then a new capture
+            self._graph_seen, self._graph_sig = self.graph_warmup - 1, None
+        if cap is None:
+            if self._graph_sig is None:
+                self._graph_sig = key[0]  # the signature the capture will be made for
+            if key[0] != self._graph_sig or self._graph_seen < self.graph_warmup:
+                if key[0] == self._graph_sig:
+                    self._graph_seen += 1
+                return self._graph_eager(batch, batch_idx, side=True)
+            self._graph_capture(batch, batch_idx, key)
+            cap = self._capture
+        elif cap[0][0] != key[0]:  # another signature (an epoch's short last batch): one eager step, the capture stays
+            return self._graph_eager(batch, batch_idx, side=False)
+        _key, graph, static, outs, slogged, _held = cap
+        for k, v in batch.items():
+            if hasattr(v, "data_ptr"):
+                static[k].copy_(v)
+        graph.replay()
+        self.graph_stats["replayed"] += 1
+        if slogged:
+            self.module.logged.update(slogged)
+        return self._copies(outs)
 
     def _toggle(self, i: int) -> None:
         for j, net in enumerate(self.nets):
@@ -298,6 +515,10 @@ class Trainer:
 
     def training_batch(self, batch: Dict[str, Any], batch_idx: int, last: bool = False) -> List[Any]:
         """One batch through every optimizer.  ``last``: no batch follows, so an open accumulation window steps now."""
+        if self.graph_steps:
+            outs = self._graph_batch(batch, batch_idx)
+            self._set_progress(self.current_epoch, self.global_step + 1)
+            return outs
         outs = []
         nopt = len(self.optimizers)
         k = self.accumulate_grad_batches
@@ -334,6 +555,7 @@ class Trainer:
         if self.accumulate_grad_batches == 1:
             for idx, b in enumerate(batches):
                 outs.append(self.training_batch(b, idx))
+            self.flush_graph_state()
             return outs
         it = iter(batches)  # one batch ahead: the last batch closes an open accumulation window
         try:
@@ -379,6 +601,12 @@ class Trainer:
         return False
 
     def _fit_epochs(self, dm):
+        try:
+            return self._fit_epochs_loop(dm)
+        finally:
+            self.flush_graph_state()
+
+    def _fit_epochs_loop(self, dm):
         if dm is None:
             raise ValueError("fit() without batches needs a datamodule: fit(datamodule=dm) or Trainer(datamodule=dm)")
         train = dm.train_dataloader()
@@ -396,6 +624,7 @@ class Trainer:
                 break
             if val is not None and (epoch + 1) % self.check_val_every_n_epoch == 0:
                 self._eval_loop("val", _limited(val, self.limit_val_batches, "limit_val_batches"))
+                self.flush_graph_state()
                 for cb in self.callbacks:
                     cb.on_validation_end(self)
             if self.should_stop:
@@ -485,6 +714,7 @@ class Trainer:
         return self._floats(self._eval_loop("test", loader, per_image=per_image, baselines=baselines))
 
     def save_checkpoint(self, path: str):
+        self.flush_graph_state()
         return self.module.save_checkpoint(path, epoch=self.current_epoch, global_step=self.global_step,
                                            optimizers=self.optimizers, schedulers=self.schedulers)
 

@@ -392,6 +392,71 @@ extern "C" int climsr_adamw_hparams(double* state, int total_steps, double max_l
   return check_launch("adamw_hparams");
 }
 
+// The same hp row for the other schedules a captured step needs: no scheduler, and five of the transformers lambdas
+// (lr = base_lr * lambda(last_epoch), transformers/optimization.py).  warmup is a double: the task's compute_warmup
+// multiplies a float ratio by the step count without rounding, and the host lambdas use the product as it is.  At
+// last_epoch 0 a warm-up schedule gives lr = 0 and the update still takes that step (m and v move), as torch's does.
+__global__ void opt_hparams_kernel(double* state, int kind, double base_lr, double beta1, double beta2, double eps, double wd,
+                                   double warmup, double total, double cycles, float* hp) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const double step = state[0] + 1.0;  // optimizer step about to be taken
+  const double s = state[1];           // scheduler last_epoch
+  double lam = 1.0;
+  if (kind >= CLIMSR_SCHED_CONSTANT_WARMUP && s < warmup) {
+    lam = s / fmax(1.0, warmup);
+  } else if (kind == CLIMSR_SCHED_LINEAR_WARMUP) {
+    lam = fmax(0.0, (total - s) / fmax(1.0, total - warmup));
+  } else if (kind == CLIMSR_SCHED_COSINE_WARMUP) {
+    const double progress = (s - warmup) / fmax(1.0, total - warmup);
+    lam = fmax(0.0, 0.5 * (1.0 + cos(M_PI * cycles * 2.0 * progress)));
+  } else if (kind == CLIMSR_SCHED_COSINE_RESTARTS_WARMUP) {
+    const double progress = (s - warmup) / fmax(1.0, total - warmup);
+    lam = progress >= 1.0 ? 0.0 : fmax(0.0, 0.5 * (1.0 + cos(M_PI * fmod(cycles * progress, 1.0))));
+  }
+  const double lr = base_lr * lam;
+  const double bc1 = 1.0 - pow(beta1, step);
+  const double bc2 = 1.0 - pow(beta2, step);
+  hp[0] = (float)lr;
+  hp[1] = (float)beta1;
+  hp[2] = (float)beta2;
+  hp[3] = (float)eps;
+  hp[4] = (float)wd;
+  hp[5] = (float)(lr / bc1);
+  hp[6] = (float)sqrt(bc2);
+  hp[7] = 0.f;
+  state[0] = step;
+  state[1] = s + 1.0;
+}
+
+extern "C" int climsr_opt_hparams(double* state, int kind, double lr, double beta1, double beta2, double eps, double wd,
+                                  double warmup, double total, double cycles, double pct_start, double div_factor,
+                                  double final_div_factor, float* hp, void* stream) {
+  if (!state || !hp || kind < CLIMSR_SCHED_ONECYCLE || kind > CLIMSR_SCHED_COSINE_RESTARTS_WARMUP || !(lr >= 0.0) ||
+      !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(wd >= 0.0)) {
+    set_error("opt_hparams: bad args");
+    return CLIMSR_EINVAL;
+  }
+  if (kind == CLIMSR_SCHED_ONECYCLE) {
+    // the kernel climsr_adamw_hparams launches, so the two agree bit for bit by construction (beta1 is cycled 0.95 <-> 0.85)
+    if (!(total >= 2.0 && total <= 2147483647.0) || total != (double)(int)total || !(pct_start > 0.0 && pct_start <= 1.0) ||
+        !(div_factor > 0.0) || !(final_div_factor > 0.0)) {
+      set_error("opt_hparams: bad OneCycleLR args");
+      return CLIMSR_EINVAL;
+    }
+    hipLaunchKernelGGL(adamw_hparams_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, (int)total, lr, pct_start, div_factor,
+                       final_div_factor, beta2, eps, wd, hp);
+    return check_launch("opt_hparams");
+  }
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || (kind >= CLIMSR_SCHED_CONSTANT_WARMUP && !(warmup >= 0.0)) ||
+      (kind >= CLIMSR_SCHED_LINEAR_WARMUP && !(total >= 0.0)) || (kind >= CLIMSR_SCHED_COSINE_WARMUP && !(cycles >= 0.0))) {
+    set_error("opt_hparams: bad schedule args");
+    return CLIMSR_EINVAL;
+  }
+  hipLaunchKernelGGL(opt_hparams_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, kind, lr, beta1, beta2, eps, wd, warmup,
+                     total, cycles, hp);
+  return check_launch("opt_hparams");
+}
+
 // torch.optim.AdamW (amsgrad=False) single-tensor semantics in fp32:
 //   p *= 1 - lr*wd; m = b1*m + (1-b1)*g; v = b2*v + (1-b2)*g*g; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
 // mirror (optional): bf16 copy of the updated p[lo, lo + mn) into mirror[0, mn) -- the MFMA operand of a layer whose
@@ -515,4 +580,80 @@ extern "C" int climsr_adamw_step_scaled(int64_t n, float* p, const float* g, flo
   hipLaunchKernelGGL(adamw_scaled_kernel, dim3(ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream, (long)n, p, g, m, v, hp,
                      gscale, mirror, mirror ? (long)mirror_lo : 0L, mirror ? (long)mirror_n : 0L);
   return check_launch("adamw_step_scaled");
+}
+
+// torch.optim.Adam (amsgrad=False) with its coupled L2 term, single-tensor semantics in fp32:
+//   G = g + wd*p; m = m + (G - m)*(1-b1); v = b2*v + (1-b2)*G*G; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
+// One element function serves the plain and the scaled entry (SCALED: g is multiplied by the clip coefficient c and
+// rounded to fp32 first), the 16-byte body and the tail alike.  Contraction is off inside it and each fused
+// multiply-add is written out, so the two entries are bit-identical at c == 1 and on a gradient multiplied beforehand
+// in fp32 whatever the compiler would have fused.
+template <bool SCALED>
+__device__ __forceinline__ void adam_elem(float& p, float g, float c, float& m, float& v, float wd, float omb1, float omb2,
+                                          float b2, float eps, float step_size, float bc2s) {
+#pragma clang fp contract(off)
+  float G = SCALED ? g * c : g;
+  G = fmaf(wd, p, G);
+  m = fmaf(omb1, G - m, m);
+  v = fmaf(omb2, G * G, b2 * v);
+  p = fmaf(-step_size, m / (sqrtf(v) / bc2s + eps), p);
+}
+template <bool SCALED>
+__global__ void adam_kernel(long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                            float* __restrict__ v, const float* __restrict__ hp, const float* __restrict__ gscale,
+                            uint16_t* __restrict__ mirror, long mlo, long mn) {
+  const float b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4], step_size = hp[5], bc2s = hp[6];
+  const float c = SCALED ? gscale[0] : 1.f;
+  const float omb1 = 1.f - b1, omb2 = 1.f - b2;
+  long i4 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i4 + 3 < n) {
+    float4 pp = *(float4*)(p + i4), gg = *(const float4*)(g + i4), mm = *(float4*)(m + i4), vv = *(float4*)(v + i4);
+    float* P = (float*)&pp; const float* G = (const float*)&gg; float* M = (float*)&mm; float* V = (float*)&vv;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) adam_elem<SCALED>(P[k], G[k], c, M[k], V[k], wd, omb1, omb2, b2, eps, step_size, bc2s);
+    *(float4*)(p + i4) = pp; *(float4*)(m + i4) = mm; *(float4*)(v + i4) = vv;
+    if (mirror && i4 >= mlo && i4 + 3 < mlo + mn && ((i4 - mlo) & 3) == 0) {  // 8 B store of 4 bf16
+      const uint2 pk = make_uint2((uint32_t)f2bf(P[0]) | ((uint32_t)f2bf(P[1]) << 16), (uint32_t)f2bf(P[2]) | ((uint32_t)f2bf(P[3]) << 16));
+      *(uint2*)(mirror + (i4 - mlo)) = pk;
+    } else if (mirror) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) adamw_mirror(i4 + k, P[k], mirror, mlo, mn);
+    }
+  } else {
+    for (long i = i4; i < n; ++i) {
+      float pi = p[i], mi = m[i], vi = v[i];
+      adam_elem<SCALED>(pi, g[i], c, mi, vi, wd, omb1, omb2, b2, eps, step_size, bc2s);
+      p[i] = pi; m[i] = mi; v[i] = vi;
+      adamw_mirror(i, pi, mirror, mlo, mn);
+    }
+  }
+}
+
+static bool adam_args_ok(int64_t n, const void* p, const void* g, const void* m, const void* v, const void* hp, int64_t mirror_lo,
+                         int64_t mirror_n, const void* mirror) {
+  return p && g && m && v && hp && n > 0 && (!mirror || (mirror_lo >= 0 && mirror_n > 0 && mirror_lo + mirror_n <= n));
+}
+
+extern "C" int climsr_adam_step(int64_t n, float* p, const float* g, float* m, float* v, const float* hp, int64_t mirror_lo,
+                                int64_t mirror_n, uint16_t* mirror, void* stream) {
+  if (!adam_args_ok(n, p, g, m, v, hp, mirror_lo, mirror_n, mirror)) {
+    set_error("adam_step: bad args");
+    return CLIMSR_EINVAL;
+  }
+  long threads = (n + 3) / 4;
+  hipLaunchKernelGGL(adam_kernel<false>, dim3(ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream, (long)n, p, g, m, v, hp,
+                     (const float*)nullptr, mirror, mirror ? (long)mirror_lo : 0L, mirror ? (long)mirror_n : 0L);
+  return check_launch("adam_step");
+}
+
+extern "C" int climsr_adam_step_scaled(int64_t n, float* p, const float* g, float* m, float* v, const float* hp,
+                                       const float* gscale, int64_t mirror_lo, int64_t mirror_n, uint16_t* mirror, void* stream) {
+  if (!adam_args_ok(n, p, g, m, v, hp, mirror_lo, mirror_n, mirror) || !gscale) {
+    set_error("adam_step_scaled: bad args");
+    return CLIMSR_EINVAL;
+  }
+  long threads = (n + 3) / 4;
+  hipLaunchKernelGGL(adam_kernel<true>, dim3(ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream, (long)n, p, g, m, v, hp,
+                     gscale, mirror, mirror ? (long)mirror_lo : 0L, mirror ? (long)mirror_n : 0L);
+  return check_launch("adam_step_scaled");
 }

@@ -275,6 +275,34 @@ int climsr_mse_loss_grad(const float* a, const float* b, int64_t n, const float*
  * hp out: {lr, beta1, beta2, eps, wd, step_size=lr/bc1, bc2_sqrt, 0}. */
 int climsr_adamw_hparams(double* state, int total_steps, double max_lr, double pct_start, double div_factor,
                          double final_div_factor, double beta2, double eps, double wd, float* hp, void* stream);
+/* Schedule kinds of climsr_opt_hparams. */
+enum {
+  CLIMSR_SCHED_ONECYCLE = 0,               /* torch OneCycleLR, cos annealing, beta1 cycled 0.95 <-> 0.85 */
+  CLIMSR_SCHED_NONE = 1,                   /* no scheduler: lr constant */
+  CLIMSR_SCHED_CONSTANT = 2,               /* transformers.get_constant_schedule */
+  CLIMSR_SCHED_CONSTANT_WARMUP = 3,        /* get_constant_schedule_with_warmup */
+  CLIMSR_SCHED_LINEAR_WARMUP = 4,          /* get_linear_schedule_with_warmup */
+  CLIMSR_SCHED_COSINE_WARMUP = 5,          /* get_cosine_schedule_with_warmup (cycles = num_cycles) */
+  CLIMSR_SCHED_COSINE_RESTARTS_WARMUP = 6  /* get_cosine_with_hard_restarts_schedule_with_warmup */
+};
+/* The hp row of climsr_adamw_hparams for any of the schedules above (one thread, fp64; state[0] the optimizer step
+ * count and state[1] the scheduler's last_epoch, both incremented here).  ONECYCLE reads lr (= max_lr), total
+ * (= total_steps, an integer >= 2), pct_start, div_factor, final_div_factor and is bit-identical to
+ * climsr_adamw_hparams (beta1 is ignored: it is cycled).  The others give lr * lambda(last_epoch) with transformers'
+ * formulas: linear warm-up s / max(1, warmup) while s < warmup (warmup may be fractional), then the kind's decay over
+ * max(1, total - warmup); parameters a kind does not use are ignored. */
+int climsr_opt_hparams(double* state, int kind, double lr, double beta1, double beta2, double eps, double wd, double warmup,
+                       double total, double cycles, double pct_start, double div_factor, double final_div_factor, float* hp,
+                       void* stream);
+/* Fused torch.optim.Adam (coupled L2: G = g + wd * p, then the AdamW moments and step without the decoupled decay)
+ * over flat fp32 buffers, hp as above.  mirror may be NULL (then mirror_lo / mirror_n are ignored); otherwise
+ * bf16(p[mirror_lo + i]) is written to mirror[i] for i < mirror_n. */
+int climsr_adam_step(int64_t n, float* p, const float* g, float* m, float* v, const float* hp, int64_t mirror_lo,
+                     int64_t mirror_n, uint16_t* mirror, void* stream);
+/* The same update on g * gscale[0] (device scalar; the product rounded to fp32 first): bit-identical to climsr_adam_step
+ * fed a gradient pre-multiplied in fp32, and to it as it stands when gscale[0] == 1.  g is not modified. */
+int climsr_adam_step_scaled(int64_t n, float* p, const float* g, float* m, float* v, const float* hp, const float* gscale,
+                            int64_t mirror_lo, int64_t mirror_n, uint16_t* mirror, void* stream);
 /* Fused AdamW over flat fp32 buffers (conf/optimizers/adamw.yaml). */
 int climsr_adamw_step(int64_t n, float* p, const float* g, float* m, float* v, const float* hp, void* stream);
 /* The same update, also writing bf16(p[mirror_lo + i]) to mirror[i] for i < mirror_n (the bf16 MFMA copy of a
