@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "conv_ep.h"
+#include "conv_route.h"
 
 namespace climsr {
 
@@ -28,20 +29,6 @@ void set_error(const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
-}
-
-// dry run (climsr_conv2d_fwd_kernel): the dispatcher records the kernel it would launch instead of launching
-static thread_local bool g_dry = false;
-static thread_local char g_dry_name[96] = "";
-
-// true (and the kernel's name recorded) when the dispatcher runs dry: the caller returns before launching
-static bool dry_run(const char* fmt, ...) {
-  if (!g_dry) return false;
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_dry_name, sizeof(g_dry_name), fmt, ap);
-  va_end(ap);
-  return true;
 }
 
 int check_launch(const char* what) {
@@ -115,14 +102,7 @@ static inline int xpitch(int cc) { return cc + ((16 - cc % 32) + 32) % 32; }  //
 // Stride 2: a fragment's 16 pixels sit 2 pixels apart in the tile, so the lane pitch is 2 * ccp and ccp == 8 (mod 16)
 // keeps it at 16 (mod 32) (the stride-1 pitch left every stride-2 read 4-way conflicted: SQ_LDS_BANK_CONFLICT 35 %).
 static inline int xpitch_s2(int cc) { return cc + ((8 - cc % 16) + 16) % 16; }
-constexpr int WPAD = 16;          // k padding of the LDS weight tile rows (kcpad is a multiple of 32)
 constexpr int FWD_LDS_BUDGET = 80 * 1024;  // two workgroups per CU
-constexpr int FWD_MAXV = 8;             // 16 B staging vectors per thread held in registers (prefetch)
-
-struct FwdGeom {
-  int th, tph, tpw, ccp, kc, kcpad, nchunk, kpk, nt, mw;
-  size_t lds_tab, lds_x, lds_w, lds_total;
-};
 
 static int fwd_nt(int out_c) {
   int nt = (out_c + 15) / 16;
@@ -177,9 +157,7 @@ extern "C" int climsr_conv_chunk_ex(int in_c, int ks, int out_c, int stride) {
   FwdGeom g;
   while (cc > 8) {
     fwd_geom(in_c, ks, 1, out_c, cc, 4, &g);
-    long nvec = (long)g.tph * g.tpw * (cc / 8) + (long)g.nt * 16 * (g.kcpad / 8);
     if (g.lds_total <= (size_t)FWD_LDS_BUDGET) break;
-    (void)nvec;
     cc = round_up((cc + 1) / 2, 8);
   }
   return cc;
@@ -348,459 +326,6 @@ extern "C" int climsr_pack_pull_weights_batched(const ClimsrPullPackDesc* descs,
   return check_launch("pack_pull_weights_batched");
 }
 
-// PF > 0: software-pipelined chunks.  Chunk j+1's input and weight vectors (at most PFX + PFW per thread) are
-// loaded into registers while chunk j is on the MFMA pipe, so a multi-chunk tile (RDB conv5 / pull-x: four
-// 32-channel chunks) pays one staging latency instead of one per chunk.
-#ifndef CLIMSR_DIAG_MODE
-#define CLIMSR_DIAG_MODE 0  // diagnostic builds only: 4 = GEO k-loop MFMAs without per-k-step fragment reads, 1 = every chunk computed twice, 2 = one staging, compute only,
-                            // 3 = staging only (GEO 1)
-#endif
-// GEO (host-checked geometry specialisation, 0 = runtime geometry): 1 / 2 = 3x3 taps over 32-channel chunks at
-// stride 1 / 2 with 16x16 output tiles (MW 4): every tap / row / fragment LDS offset is a compile-time immediate,
-// so the unrolled k-steps read their fragments with no address arithmetic and no tap-table lookup (the runtime
-// form waited on a dependent ds_read of the table each k-step, and the compiler then issued the fragment reads
-// just before their MFMAs: the compute phase alone ran at ~55 % of the MFMA rate).
-template <int MW, int NT, bool RF, int MV, int PFX, int PFW, int EP, int GEO>
-__device__ __forceinline__ void conv_fwd_body(const FwdArgs& a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  int* tab = (int*)smem;
-  uint16_t* xs = (uint16_t*)(smem + a.lds_tab);
-  uint16_t* ws = (uint16_t*)(smem + a.lds_tab + a.lds_x);
-
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6;
-  const int lane = tid & 63;
-  const int g = lane >> 4;
-  const int col = lane & 15;
-
-  // (tile, output-channel block): blockIdx, or with xgrp the XCD-major order in which the xgrp channel blocks of a
-  // tile are consecutive on one XCD (the x tile is fetched into that L2 once for all of them, not once per XCD)
-  // Stagger: the two workgroups that share a CU run the same program and start together, so they stage (global
-  // loads, LDS stores, barriers) and compute (MFMA) in lockstep -- diagnostic builds measured staging + MFMA-only
-  // times that simply add (VGG 256 @64^2: 141 + 147 us = 288 us).  The second workgroup of each CU (the second
-  // dispatch round, [stag_lo, stag_hi)) starts about half a chunk late; the blocks that replace them inherit the
-  // offset.  Speed only: nothing depends on which workgroups share a CU.
-  if (a.stag_n && (int)blockIdx.x >= a.stag_lo && (int)blockIdx.x < a.stag_hi)
-    for (int i = 0; i < a.stag_n; ++i) __builtin_amdgcn_s_sleep(32);
-  int tile_id = blockIdx.x, cob = blockIdx.y;
-  if (a.xgrp > 0) {
-    const int ntile = a.tiles_x * a.tiles_y * a.n, idx = xcd_major(blockIdx.x, gridDim.x);
-    const int grp = idx / (ntile * a.xgrp), rem = idx - grp * (ntile * a.xgrp);
-    tile_id = rem / a.xgrp;
-    cob = grp * a.xgrp + (rem - tile_id * a.xgrp);
-  }
-  int bid = tile_id;
-  const int tx = bid % a.tiles_x;
-  bid /= a.tiles_x;
-  const int ty = bid % a.tiles_y;
-  const int nimg = bid / a.tiles_y;
-  const int ox0 = tx * TW;
-  const int oy0 = ty * (4 * MW);
-  const int co_blk0 = cob * NT * 16;
-  const int wpitch = a.kcpad + WPAD;
-  const int ks2 = a.ks * a.ks;
-
-  // tap table: LDS element offset of k-group (8 channels) within a chunk
-  for (int i = tid; i < (GEO > 0 ? 0 : a.kcpad / 8); i += 256) {
-    int kr = i * 8;
-    int tap = kr / a.cc;
-    int c = kr - tap * a.cc;
-    if (tap >= ks2) { tap = 0; c = 0; }
-    int ky = tap / a.ks, kx = tap - (tap / a.ks) * a.ks;
-    tab[i] = (ky * a.tpw + kx) * a.ccp + c;
-  }
-
-  f32x4 acc[MW][NT];
-#pragma unroll
-  for (int m = 0; m < MW; ++m)
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[m][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  int pixbase[MW];
-#pragma unroll
-  for (int m = 0; m < MW; ++m) pixbase[m] = ((wave * MW + m) * a.stride * a.tpw + col * a.stride) * a.ccp;
-
-  // up = 2: nearest x2 upsample on load (src = j >> 1); up = -2: zero insertion (src = j >> 1 for even j,
-  // else 0) = the input of the data gradient of a stride-2 conv
-  const int ufac = a.up < 0 ? -a.up : a.up;
-  const int lh = a.in_h * ufac, lw = a.in_w * ufac;
-  const int iy0 = oy0 * a.stride - a.pad, ix0 = ox0 * a.stride - a.pad;
-  const int cvec = a.cc / 8;
-  const int dilmask = a.up < 0 ? 1 : 0;
-  const int nvec_x = a.tph * a.tpw * cvec;
-  const int wvec_row = a.kcpad / 8;
-  const int nvec_w = NT * 16 * wvec_row;
-  const int upsh = ufac == 2 ? 1 : 0;
-
-  // Staging index math is incremental: each thread's k-th vector is (tid + 256k); the pixel /
-  // channel-group / row decomposition of the first one costs a few divisions once per kernel, every
-  // later one only adds constants with carries (runtime integer division is ~40 VALU ops).
-  const int x_dp = 256 / cvec, x_dc = 256 - x_dp * cvec;  // +256 vectors = x_dp pixels + x_dc groups
-  const int x_dy = x_dp / a.tpw, x_dx = x_dp - x_dy * a.tpw;
-  const int x_pix0 = tid / cvec, x_cg0 = tid - x_pix0 * cvec;
-  const int x_ty0 = x_pix0 / a.tpw, x_tx0 = x_pix0 - x_ty0 * a.tpw;
-  const int w_dr = 256 / wvec_row, w_dk = 256 - w_dr * wvec_row;
-  const int w_r0 = tid / wvec_row, w_k0 = tid - w_r0 * wvec_row;
-  const int nrx = (nvec_x + 255) / 256, nrw = (nvec_w + 255) / 256;
-  // k-steps software-pipelined two deep: the fragments of k-step s+1 are read from LDS while the MFMAs of
-  // k-step s run (one wave per SIMD pair cannot hide the ds_read latency otherwise)
-  auto compute = [&]() {
-    if constexpr (GEO > 0) {
-      static_assert(MW == 4, "GEO tiles are 16 x 16");
-      constexpr int S = GEO, TPW = (TW - 1) * S + 3, CCP = S == 1 ? 48 : 40, WP = 9 * 32 + WPAD;
-      const uint16_t* xb = xs + ((wave * MW * TPW + col) * S) * CCP + g * 8;
-      const uint16_t* wb = ws + col * WP + g * 8;
-      bf16x8 af[2][NT], bf[2][MW];
-      auto ld = [&](int k, int b) {
-        const int off = ((k / 3) * TPW + (k % 3)) * CCP;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) af[b][t] = *(const bf16x8*)(wb + t * 16 * WP + k * 32);
-#pragma unroll
-        for (int m = 0; m < MW; ++m) bf[b][m] = *(const bf16x8*)(xb + m * S * TPW * CCP + off);
-      };
-      ld(0, 0);
-#pragma unroll
-      for (int k = 0; k < 9; ++k) {
-#if CLIMSR_DIAG_MODE == 4  // diagnostic build 4: the k-step fragments read once per chunk, MFMAs only
-        if (k == 0) ld(1, 1);
-#else
-        if (k + 1 < 9) ld(k + 1, (k + 1) & 1);
-#endif
-        // the next k-step's NT + MW fragment reads go out as one burst ahead of this k-step's MW x NT MFMAs (the
-        // compiler otherwise sinks each read next to its first MFMA and waits lgkmcnt(0) there: the LDS latency was
-        // exposed at nearly every k-step of the unrolled loop)
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int m = 0; m < MW; ++m)
-#pragma unroll
-          for (int t = 0; t < NT; ++t) acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[k & 1][t], bf[k & 1][m], acc[m][t], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      return;
-    }
-    const int nks = a.kcpad / 32;
-    bf16x8 afA[NT], bfA[MW], afB[NT], bfB[MW];
-    auto ld = [&](int ks, bf16x8(&af)[NT], bf16x8(&bf)[MW]) {
-      const int off = tab[ks * 4 + g];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) af[t] = *(const bf16x8*)(ws + (t * 16 + col) * wpitch + ks * 32 + g * 8);
-#pragma unroll
-      for (int m = 0; m < MW; ++m) bf[m] = *(const bf16x8*)(xs + pixbase[m] + off);
-    };
-    auto mm = [&](const bf16x8(&af)[NT], const bf16x8(&bf)[MW]) {
-#pragma unroll
-      for (int m = 0; m < MW; ++m)
-#pragma unroll
-        for (int t = 0; t < NT; ++t) acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[t], bf[m], acc[m][t], 0, 0, 0);
-    };
-    ld(0, afA, bfA);
-    int ks = 0;
-    for (; ks + 2 <= nks; ks += 2) {
-      ld(ks + 1, afB, bfB);
-      mm(afA, bfA);
-      ld(ks + 2 < nks ? ks + 2 : nks - 1, afA, bfA);  // unconditional (clamped): no branch around the reads
-      mm(afB, bfB);
-    }
-    if (ks < nks) mm(afA, bfA);  // odd k-step count: the last one is already loaded
-  };
-
-  if constexpr (PFX > 0 && GEO == 1) {
-    // Compile-time staging geometry (18 x 18-pixel x tile of 4 x 16 B channel vectors, 64 x 36 weight vectors per
-    // chunk): each thread's vector i is (tid + 256 i), so its pixel / channel group / weight row are per-thread
-    // constants; the chunk-0 byte offset of every vector is computed once (out-of-image vectors get BUF_OOB, which
-    // stays out of range at every chunk), and a chunk's loads are buffer loads at offset + j * chunk bytes -- one add
-    // per vector.  The runtime-geometry walk below spent ~570 VALU per chunk on index carries, bounds checks and
-    // 64-bit addresses (4 VALU per MFMA: the chunk loop was VALU-issue bound, conv5 / pull-x most of all).
-    // The host takes GEO 1 only for up == 1, in_c % 32 == 0 and tensors under 2 GiB.
-    constexpr int CV = 4, TPWc = TW + 2, CCPc = 48, NXV = (TW + 2) * (TW + 2) * CV, WV = 36, WPc = 9 * 32 + WPAD, NWV = NT * 16 * WV;
-    static_assert(PFX * 256 >= NXV && PFW * 256 >= NWV, "GEO 1 staging: not enough prefetch vectors");
-    uint4 px[PFX], pw[PFW];
-    const int cg8 = (tid & 3) * 8;  // 256 % CV == 0: every vector of a thread has the same channel group
-    const __amdgpu_buffer_rsrc_t xr = buf_rsrc(a.x, (uint32_t)((long)a.n * a.in_h * a.in_w * a.in_cs * 2));
-    const __amdgpu_buffer_rsrc_t wr = buf_rsrc(a.w, (uint32_t)((long)(cob + 1) * NT * 16 * a.kpk * 2));
-    uint32_t xo[PFX], wo[PFW];
-#pragma unroll
-    for (int i = 0; i < PFX; ++i) {
-      const int v = tid + 256 * i, pix = v >> 2, ty_ = pix / TPWc, tx_ = pix - ty_ * TPWc;
-      const int iy = iy0 + ty_, ix = ix0 + tx_;
-      const bool ok = v < NXV && iy >= 0 && iy < a.in_h && ix >= 0 && ix < a.in_w;
-      xo[i] = ok ? (uint32_t)((((nimg * a.in_h + iy) * a.in_w + ix) * a.in_cs + a.in_co + cg8) * 2) : BUF_OOB;
-    }
-#pragma unroll
-    for (int i = 0; i < PFW; ++i) {
-      const int v = tid + 256 * i, r = v / WV, kv = v - r * WV;
-      wo[i] = v < NWV ? (uint32_t)(((co_blk0 + r) * a.kpk + kv * 8) * 2) : BUF_OOB;
-    }
-    auto issue = [&](int j) {
-#pragma unroll
-      for (int i = 0; i < PFX; ++i) px[i] = buf_load16(xr, xo[i] + (uint32_t)j * 64u);
-#pragma unroll
-      for (int i = 0; i < PFW; ++i) pw[i] = buf_load16(wr, wo[i] + (uint32_t)j * (uint32_t)(a.kcpad * 2));
-    };
-    auto stash = [&]() {
-      // pixel (v >> 2) = (tid >> 2) + 64 i: compile-time steps; lanes past the tile dump into the pad channels 32..39
-      // of pixel 0, which no fragment reads
-      const int xl0 = (tid >> 2) * CCPc + cg8;
-#pragma unroll
-      for (int i = 0; i < PFX; ++i) {
-        const int v = tid + 256 * i;
-        *(uint4*)(xs + ((NXV % 256 == 0 || v < NXV) ? xl0 + 64 * CCPc * i : 32)) = px[i];
-      }
-#pragma unroll
-      for (int i = 0; i < PFW; ++i) {
-        const int v = tid + 256 * i, r = v / WV, kv = v - r * WV;
-        if (NWV % 256 == 0 || v < NWV) *(uint4*)(ws + r * WPc + kv * 8) = pw[i];
-      }
-    };
-    issue(0);
-#if CLIMSR_DIAG_MODE == 2
-    lds_barrier();
-    stash();
-    lds_barrier();
-    for (int j = 0; j < a.nchunk; ++j) compute();
-#else
-    for (int j = 0; j < a.nchunk; ++j) {
-      lds_barrier();  // chunk j-1's fragment reads are done
-      stash();
-      if (j + 1 < a.nchunk) issue(j + 1);  // lands while chunk j computes
-      lds_barrier();
-#if CLIMSR_DIAG_MODE != 3  // diagnostic build 3: staging only, no k-loop
-      compute();
-#endif
-    }
-#endif
-  } else if constexpr (PFX > 0) {
-    uint4 px[PFX], pw[PFW];
-    auto issue = [&](int j) {
-      int ty_ = x_ty0, tx_ = x_tx0, cg = x_cg0;
-#pragma unroll
-      for (int i = 0; i < PFX; ++i) {
-        px[i] = make_uint4(0, 0, 0, 0);
-        if (i < nrx && ty_ < a.tph) {
-          const int iy = iy0 + ty_, ix = ix0 + tx_;
-          const int c = j * a.cc + cg * 8;
-          if (iy >= 0 && iy < lh && ix >= 0 && ix < lw && c < a.in_c && !((iy | ix) & dilmask))
-            px[i] = *(const uint4*)(a.x + (((long)nimg * a.in_h + (iy >> upsh)) * a.in_w + (ix >> upsh)) * a.in_cs + a.in_co + c);
-        }
-        cg += x_dc;
-        tx_ += x_dx;
-        ty_ += x_dy;
-        if (cg >= cvec) { cg -= cvec; ++tx_; }
-        if (tx_ >= a.tpw) { tx_ -= a.tpw; ++ty_; }
-      }
-      int r = w_r0, kv = w_k0;
-#pragma unroll
-      for (int i = 0; i < PFW; ++i) {
-        pw[i] = make_uint4(0, 0, 0, 0);
-        if (i < nrw && r < NT * 16)
-          pw[i] = *(const uint4*)(a.w + (long)(co_blk0 + r) * a.kpk + (long)j * a.kcpad + kv * 8);
-        kv += w_dk;
-        r += w_dr;
-        if (kv >= wvec_row) { kv -= wvec_row; ++r; }
-      }
-    };
-    auto stash = [&]() {
-      int ty_ = x_ty0, tx_ = x_tx0, cg = x_cg0;
-#pragma unroll
-      for (int i = 0; i < PFX; ++i) {
-        if (i < nrx && ty_ < a.tph) *(uint4*)(xs + (ty_ * a.tpw + tx_) * a.ccp + cg * 8) = px[i];
-        cg += x_dc;
-        tx_ += x_dx;
-        ty_ += x_dy;
-        if (cg >= cvec) { cg -= cvec; ++tx_; }
-        if (tx_ >= a.tpw) { tx_ -= a.tpw; ++ty_; }
-      }
-      int r = w_r0, kv = w_k0;
-#pragma unroll
-      for (int i = 0; i < PFW; ++i) {
-        if (i < nrw && r < NT * 16) *(uint4*)(ws + r * wpitch + kv * 8) = pw[i];
-        kv += w_dk;
-        r += w_dr;
-        if (kv >= wvec_row) { kv -= wvec_row; ++r; }
-      }
-    };
-    issue(0);
-#if CLIMSR_DIAG_MODE == 2
-    __syncthreads();
-    stash();
-    __syncthreads();
-    for (int j = 0; j < a.nchunk; ++j) compute();
-#else
-    for (int j = 0; j < a.nchunk; ++j) {
-      __syncthreads();  // chunk j-1's fragment reads are done
-      stash();
-      if (j + 1 < a.nchunk) issue(j + 1);  // lands while chunk j computes
-      __syncthreads();
-      compute();
-#if CLIMSR_DIAG_MODE == 1
-      compute();
-#endif
-    }
-#endif
-  } else {
-  // batched staging: every thread issues up to MV input + MV weight 16 B global loads before the first
-  // LDS store, so a chunk pays ~one memory latency instead of one per vector
-  const int nbatch = nrx > nrw ? nrx : nrw;
-  for (int j = 0; j < a.nchunk; ++j) {
-    __syncthreads();
-    int ty_ = x_ty0, tx_ = x_tx0, cg = x_cg0;  // input tile (logical coordinates: upsampled / zero-inserted)
-    int r = w_r0, kv = w_k0;                  // weight chunk rows [co_blk0, co_blk0 + 16*NT) x kcpad
-    for (int base = 0; base < nbatch; base += MV) {
-      uint4 bx[MV], bw[MV];
-      int dx[MV], dw[MV];
-#pragma unroll
-      for (int i = 0; i < MV; ++i) {
-        dx[i] = -1;
-        if (base + i < nrx && ty_ < a.tph) {
-          const int iy = iy0 + ty_, ix = ix0 + tx_;
-          const int c = j * a.cc + cg * 8;
-          uint4 val = make_uint4(0, 0, 0, 0);
-          if (iy >= 0 && iy < lh && ix >= 0 && ix < lw && c < a.in_c && !((iy | ix) & dilmask))
-            val = *(const uint4*)(a.x + (((long)nimg * a.in_h + (iy >> upsh)) * a.in_w + (ix >> upsh)) * a.in_cs + a.in_co + c);
-          bx[i] = val;
-          dx[i] = (ty_ * a.tpw + tx_) * a.ccp + cg * 8;
-        }
-        cg += x_dc;
-        tx_ += x_dx;
-        ty_ += x_dy;
-        if (cg >= cvec) { cg -= cvec; ++tx_; }
-        if (tx_ >= a.tpw) { tx_ -= a.tpw; ++ty_; }
-      }
-#pragma unroll
-      for (int i = 0; i < MV; ++i) {
-        dw[i] = -1;
-        if (base + i < nrw && r < NT * 16) {
-          bw[i] = *(const uint4*)(a.w + (long)(co_blk0 + r) * a.kpk + (long)j * a.kcpad + kv * 8);
-          dw[i] = r * wpitch + kv * 8;
-        }
-        kv += w_dk;
-        r += w_dr;
-        if (kv >= wvec_row) { kv -= wvec_row; ++r; }
-      }
-#pragma unroll
-      for (int i = 0; i < MV; ++i)
-        if (dx[i] >= 0) *(uint4*)(xs + dx[i]) = bx[i];
-#pragma unroll
-      for (int i = 0; i < MV; ++i)
-        if (dw[i] >= 0) *(uint4*)(ws + dw[i]) = bw[i];
-    }
-    __syncthreads();
-    compute();
-  }
-  }
-
-  // ---------------- epilogue ----------------
-  // All global reads of the epilogue (bias, residuals, accumulate targets) are issued for every
-  // fragment before the first store, so their latencies overlap instead of serialising.
-  const int ox = ox0 + col;
-  if (EP == 0 && a.down2) {
-    // sum the 2x2 block: rows (m, m+1) are in this wave (MW even, oy0 even); columns pair via lane^1.
-    // Optional activation backward (act 3/4, res1 = the activation output at the LOW-res pixel), bf16 or
-    // fp32 (=, +=) store and a bf16 aux copy.
-    const int dh = a.out_h >> 1, dw = a.out_w >> 1;
-    const bool mask = a.act == 3 || a.act == 4;
-    float4 old[MW / 2][NT];
-    uint2 r1v[MW / 2][NT];
-    const __amdgpu_buffer_rsrc_t ry2 = opt_rsrc(a.out_mode == 2 ? a.y : nullptr), rm1 = opt_rsrc(mask ? a.res1 : nullptr);
-#pragma unroll
-    for (int m = 0; m < MW; m += 2) {
-      const int oy = oy0 + wave * MW + m;
-      const long pidx = ((long)nimg * dh + (oy >> 1)) * dw + (ox >> 1);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const int co = co_blk0 + t * 16 + g * 4;
-        const bool ok = (col & 1) == 0 && oy < a.out_h && ox < a.out_w && co + 3 < a.out_c;
-        const long q = ok ? pidx : 0;
-        const uint4 o4 = buf_load16(ry2, (uint32_t)((q * a.out_cs + (ok ? a.out_co + co : 0)) * 4));
-        old[m / 2][t] = make_float4(__uint_as_float(o4.x), __uint_as_float(o4.y), __uint_as_float(o4.z), __uint_as_float(o4.w));
-        r1v[m / 2][t] = buf_load8(rm1, (uint32_t)((q * a.r1_cs + (ok ? a.r1_co + co : 0)) * 2));
-      }
-    }
-#pragma unroll
-    for (int m = 0; m < MW; m += 2) {
-      const int oy = oy0 + wave * MW + m;
-      const long pidx = ((long)nimg * dh + (oy >> 1)) * dw + (ox >> 1);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        float v[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          float sm = acc[m][t][i] + acc[m + 1][t][i];
-          sm += __shfl_xor(sm, 1);
-          v[i] = sm;
-        }
-        const int co = co_blk0 + t * 16 + g * 4;
-        if ((col & 1) == 0 && oy < a.out_h && ox < a.out_w) {
-          const long ob = pidx * a.out_cs + a.out_co + co;
-          if (co + 3 < a.out_c) {
-            const uint4 r1 = make_uint4(r1v[m / 2][t].x, r1v[m / 2][t].y, 0, 0);
-            if (mask) {
-#pragma unroll
-              for (int i = 0; i < 4; ++i) v[i] = ep_res(v[i], a.act, a.slope, true, res4_at(r1, false, i), 1.f, 1.f, false, 0.f, 1.f, 1.f);
-            }
-            if (a.out_mode == 0) {
-              uint2 pk;
-              pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-              pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-              *(uint2*)((uint16_t*)a.y + ob) = pk;
-            } else {
-              float4 o = old[m / 2][t];
-              *(float4*)((float*)a.y + ob) = make_float4(o.x + v[0], o.y + v[1], o.z + v[2], o.w + v[3]);
-            }
-            if (a.aux) {
-              uint2 pk;
-              pk.x = (uint32_t)f2bf(a.aux_scale * v[0]) | ((uint32_t)f2bf(a.aux_scale * v[1]) << 16);
-              pk.y = (uint32_t)f2bf(a.aux_scale * v[2]) | ((uint32_t)f2bf(a.aux_scale * v[3]) << 16);
-              *(uint2*)(a.aux + pidx * a.aux_cs + a.aux_co + co) = pk;
-            }
-          } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              if (co + i >= a.out_c) continue;
-              float x = v[i];
-              if (mask) x = ep_res(x, a.act, a.slope, true, res_at(a.res1, false, pidx * a.r1_cs + a.r1_co + co + i), 1.f, 1.f, false,
-                                   0.f, 1.f, 1.f);
-              if (a.out_mode == 0) ((uint16_t*)a.y)[ob + i] = f2bf(x);
-              else if (a.out_mode == 2) ((float*)a.y)[ob + i] += x;
-              else ((float*)a.y)[ob + i] = x;
-              if (a.aux) a.aux[pidx * a.aux_cs + a.aux_co + co + i] = f2bf(a.aux_scale * x);
-            }
-          }
-        }
-      }
-    }
-    return;
-  }
-  // coalesced epilogue: the wave's MW x 16 pixels x 16 NT channels go through its own LDS region
-  constexpr int EPP = NT * 16 + 4;  // LDS pitch (floats) of a staged pixel
-  float* eb = (float*)smem + wave * (MW * 16 * EPP);
-  __syncthreads();  // every wave is done with the staged operands (the regions alias them)
-#pragma unroll
-  for (int m = 0; m < MW; ++m)
-#pragma unroll
-    for (int t = 0; t < NT; ++t) *(f32x4*)(eb + (m * 16 + col) * EPP + t * 16 + g * 4) = acc[m][t];
-  __syncthreads();  // orders the staging writes before the transposed reads (they use another vector type)
-  if constexpr (EP == 9 || EP == 10) {
-    static_assert(MW == 4 && NT == 4, "BatchNorm partials: 16x16 x 64-channel tiles");
-    float ssum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ssq[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    store_tile_lds<RF, MW * 16, NT * 16, 64, EP>(a, eb, EPP, lane, nimg, oy0 + wave * MW, ox0, co_blk0, ssum, ssq);
-    bn_tile_partials(a, ssum, ssq, true, wave, lane, tile_id, co_blk0, (float*)smem);
-  } else {
-    store_tile_lds<RF, MW * 16, NT * 16, 64, EP>(a, eb, EPP, lane, nimg, oy0 + wave * MW, ox0, co_blk0);
-  }
-}
-
-// two workgroups per CU (<= 80 KiB LDS each): at most 256 registers so that two waves share each SIMD
-template <int MW, int NT, bool RF, int MV, int PFX = 0, int PFW = 0, int EP = 0, int GEO = 0>
-__global__ __launch_bounds__(256, 2) void conv_fwd_kernel(FwdArgs a) {
-  conv_fwd_body<MW, NT, RF, MV, PFX, PFW, EP, GEO>(a);
-}
-// large stride-2 input tiles (one workgroup per CU): the deep prefetch may use the whole register file
-template <int MW, int NT, bool RF, int MV, int PFX = 0, int PFW = 0, int EP = 0, int GEO = 0>
-__global__ __launch_bounds__(256) void conv_fwd_wide_kernel(FwdArgs a) {
-  conv_fwd_body<MW, NT, RF, MV, PFX, PFW, EP, GEO>(a);
-}
-
 // ------------------------------------------------------------------------------------------
 // Dense-block conv with <= 16 output channels (RDB conv1-4, esrgan.py:22-25, and their pull data
 // gradients): 3x3, stride 1, pad 1, <= 128 input channels.  One 16-row MFMA tile of outputs leaves the
@@ -817,26 +342,6 @@ __global__ __launch_bounds__(256) void conv_fwd_wide_kernel(FwdArgs a) {
 // ------------------------------------------------------------------------------------------
 constexpr int N16_TH = 8;
 constexpr int N16_TPH = N16_TH + 2, N16_TPW = TW + 2;
-
-// Persistent tile walk, XCD-aware.  Workgroups are dispatched round-robin over the 8 XCDs and each XCD
-// has its own L2, so block b walks a contiguous span of tiles owned by XCD b % 8: tiles that run at the
-// same time on one XCD are spatial neighbours and share their input halo rows in that L2.
-struct TileWalk {
-  int first, step, end;
-  __device__ explicit TileWalk(int ntiles) {
-    const int grid = (int)gridDim.x, b = (int)blockIdx.x;
-    if (grid % 8 == 0 && grid >= 64) {
-      const int span = (ntiles + 7) / 8, xcd = b % 8;
-      first = xcd * span + b / 8;
-      step = grid / 8;
-      end = min(ntiles, (xcd + 1) * span);
-    } else {
-      first = b;
-      step = grid;
-      end = ntiles;
-    }
-  }
-};
 
 static int n16_ncb(int in_c) { return in_c <= 32 ? 1 : (in_c <= 64 ? 2 : 4); }
 
@@ -1026,10 +531,6 @@ __global__ __launch_bounds__(256, NCB == 4 ? 2 : 3) void conv_n16_kernel(FwdArgs
 
 template <int NCB, int EP>
 static int launch_n16(const FwdArgs& a, hipStream_t s) {
-  if (g_dry) {
-    snprintf(g_dry_name, sizeof(g_dry_name), "conv_n16_kernel<%d, %d>", NCB, EP);
-    return CLIMSR_OK;
-  }
   auto k = conv_n16_kernel<NCB, EP>;
   size_t lds = (size_t)N16_TPH * N16_TPW * (NCB * 32 + 16) * 2;
   const size_t lds_p = (size_t)NCB * N16_TH * 64 * 16;             // partial sums (aliased)
@@ -1150,25 +651,9 @@ __global__ __launch_bounds__(256, 2) void conv_co1m_kernel(FwdArgs a) {
 
 template <int KS, int NCH>
 static int launch_co1m(const FwdArgs& a, hipStream_t s) {
-  if (g_dry) {
-    snprintf(g_dry_name, sizeof(g_dry_name), "conv_co1m_kernel<%d, %d>", KS, NCH);
-    return CLIMSR_OK;
-  }
   dim3 grid(ceil_div(a.out_w, CO1M_COLS), ceil_div(a.out_h, 4 * CO1M_ROWS), a.n);
   hipLaunchKernelGGL((conv_co1m_kernel<KS, NCH>), grid, dim3(256), 0, s, a);
   return check_launch("conv2d_fwd (co1m)");
-}
-
-static int dispatch_co1m(const ClimsrConvDesc* d, const FwdArgs& a, hipStream_t s) {
-  const int nch = d->in_c <= 32 ? 1 : 2;
-  switch (d->ks * 10 + nch) {
-    case 31: return launch_co1m<3, 1>(a, s);
-    case 32: return launch_co1m<3, 2>(a, s);
-    case 51: return launch_co1m<5, 1>(a, s);
-    case 52: return launch_co1m<5, 2>(a, s);
-    case 91: return launch_co1m<9, 1>(a, s);
-    default: return launch_co1m<9, 2>(a, s);
-  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1265,20 +750,8 @@ __global__ __launch_bounds__(256) void conv_co1_kernel(FwdArgs a) {
   if (a.aux) a.aux[pidx * a.aux_cs + a.aux_co] = f2bf(a.aux_scale * v);
 }
 
-// ------------------------------------------------------------------------------------------
-// Weights-resident persistent conv: one workgroup per CU stages the WHOLE packed weight matrix
-// (<= 64 output channels, one channel chunk) into LDS once and walks its share of the output tiles,
-// the next tile's input prefetched into registers while the current one is on the MFMA pipe.  For the
-// HR-resolution convs (HRconv / upconv1-2 with the upsample on load, srcnn.conv1 9x9 and conv2 5x5,
-// their data gradients, trunk_conv / conv_first) the generic kernel restages the weights for every
-// 256-pixel tile (8k tiles per launch at 256^2).  Stride 1 only; epilogue = the generic one.
-// ------------------------------------------------------------------------------------------
+// Geometry of the weights-resident persistent conv (conv_pw.hip)
 constexpr int PW_PV = 12;  // prefetched 16 B input vectors per thread (tile <= 3072 vectors)
-
-struct PwGeom {
-  int mw, tph, tpw, ccp, kcpad, nvx;
-  size_t lds_tab, lds_w, lds_x, lds_ep, lds_total;
-};
 
 static bool pw_geom(const ClimsrConvDesc* d, int nt, int mw, PwGeom* g, int nw = 4) {
   if (d->stride != 1 || d->cc < d->in_c) return false;
@@ -1307,315 +780,6 @@ static bool pw_fits(int in_c, int ks, int out_c) {
   d.stride = 1;
   PwGeom g;
   return pw_geom(&d, nt, 2, &g, 4);
-}
-
-// GEO = 1: 3x3 taps over one 64-channel chunk with 8 waves x 2 rows (the 64 -> 64 HR-resolution / VGG conv1_2
-// shapes): the 18 k-steps unrolled with compile-time LDS offsets (no tap table; see conv_fwd_kernel's GEO)
-template <int NW, int MW, int NT, bool RF, int PV, int EP = 0, int GEO = 0>
-__global__ __launch_bounds__(64 * NW, 1) void conv_pw_kernel(FwdArgs a) {
-  constexpr int NTHR = 64 * NW;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  int* tab = (int*)smem;
-  uint16_t* ws = (uint16_t*)(smem + a.lds_tab);
-  uint16_t* xs = (uint16_t*)(smem + a.lds_tab + a.lds_x);  // lds_x carries the weight region size here
-  float* ebase = (float*)xs;                               // epilogue staging aliases the input tile
-
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, col = lane & 15;
-  const int wpitch = a.kcpad + WPAD;
-  const int ks2 = a.ks * a.ks;
-  if constexpr (GEO == 2) {  // 4-channel taps: table of tap offsets, one per 4 k values
-    for (int i = tid; i < a.kcpad / 4; i += NTHR) {
-      const int tap = i < ks2 ? i : 0, ky = tap / a.ks, kx = tap - ky * a.ks;
-      tab[i] = (ky * a.tpw + kx) * a.ccp;
-    }
-  }
-  for (int i = tid; i < (GEO ? 0 : a.kcpad / 8); i += NTHR) {  // tap table (one chunk)
-    const int kr = i * 8;
-    int tap = kr / a.cc, c = kr - tap * a.cc;
-    if (tap >= ks2) { tap = 0; c = 0; }
-    const int ky = tap / a.ks, kx = tap - ky * a.ks;
-    tab[i] = (ky * a.tpw + kx) * a.ccp + c;
-  }
-  {  // the whole weight matrix, once: 8 vectors per thread in flight per batch (buffer loads, no branch)
-    const int wvec_row = a.kcpad / 8, nvw = NT * 16 * wvec_row;
-    const __amdgpu_buffer_rsrc_t wr = buf_rsrc(a.w, 0xFFFFFFFFu);
-    for (int v0 = 0; v0 < nvw; v0 += 8 * NTHR) {
-      uint4 wv[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int v = v0 + tid + i * NTHR;
-        const int r = v / wvec_row, kv = v - r * wvec_row;
-        wv[i] = buf_load16(wr, v < nvw ? (uint32_t)((r * a.kpk + kv * 8) * 2) : 0u);
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int v = v0 + tid + i * NTHR;
-        const int r = v / wvec_row, kv = v - r * wvec_row;
-        if (v < nvw) *(uint4*)(ws + r * wpitch + kv * 8) = wv[i];
-      }
-    }
-  }
-  const int ufac = a.up, upsh = a.up == 2 ? 1 : 0;
-  const int lh = a.in_h * ufac, lw = a.in_w * ufac;
-  const int cvec = a.cc / 8;
-  const int nvec_x = a.tph * a.tpw * cvec;
-  const int x_dp = NTHR / cvec, x_dc = NTHR - x_dp * cvec;
-  const int x_dy = x_dp / a.tpw, x_dx = x_dp - x_dy * a.tpw;
-  const int x_pix0 = tid / cvec, x_cg0 = tid - x_pix0 * cvec;
-  const int x_ty0 = x_pix0 / a.tpw, x_tx0 = x_pix0 - x_ty0 * a.tpw;
-  const int ntiles = a.tiles_x * a.tiles_y * a.n;
-
-  uint4 pre[PV];
-  // buffer loads (zeros out of range) and an unconditional call: the next tile's loads stay in flight
-  // through this tile's compute (see conv_n16_kernel)
-  const __amdgpu_buffer_rsrc_t xr = buf_rsrc(a.x, (uint32_t)((long)a.n * a.in_h * a.in_w * a.in_cs * 2));
-  // tile coordinates advance incrementally by the walk's step (no per-tile integer divisions: wave-uniform
-  // divisions by runtime tile counts cost ~40 SALU each, 8 per tile, on the CU's shared scalar pipe)
-  auto issue = [&](bool live, int tx, int ty, int nimg) {  // !live: nothing to load
-    const int iy0 = ty * (NW * MW) - a.pad, ix0 = tx * TW - a.pad;
-    int ty_ = x_ty0, tx_ = x_tx0, cg = x_cg0;
-#pragma unroll
-    for (int i = 0; i < PV; ++i) {
-      {
-        const int iy = iy0 + ty_, ix = ix0 + tx_;
-        const int c = cg * 8;
-        const bool ok = live && tid + NTHR * i < nvec_x && iy >= 0 && iy < lh && ix >= 0 && ix < lw && c < a.in_c;
-        const uint32_t off = (uint32_t)((((nimg * a.in_h + (iy >> upsh)) * a.in_w + (ix >> upsh)) * a.in_cs + a.in_co + c) * 2);
-        pre[i] = buf_load16(xr, ok ? off : BUF_OOB);
-      }
-      cg += x_dc;
-      tx_ += x_dx;
-      ty_ += x_dy;
-      if (cg >= cvec) { cg -= cvec; ++tx_; }
-      if (tx_ >= a.tpw) { tx_ -= a.tpw; ++ty_; }
-    }
-  };
-  const TileWalk walk(ntiles);
-  const int s_x = walk.step % a.tiles_x, s_y = (walk.step / a.tiles_x) % a.tiles_y, s_n = walk.step / (a.tiles_x * a.tiles_y);
-  auto advance = [&](int& tx, int& ty, int& n) {
-    tx += s_x;
-    int c = tx >= a.tiles_x;
-    tx -= c ? a.tiles_x : 0;
-    ty += s_y + c;
-    c = ty >= a.tiles_y;
-    ty -= c ? a.tiles_y : 0;
-    n += s_n + c;
-  };
-  int ctx = walk.first % a.tiles_x, cty = (walk.first / a.tiles_x) % a.tiles_y, cn = walk.first / (a.tiles_x * a.tiles_y);
-  if (walk.first < walk.end) issue(true, ctx, cty, cn);
-
-  int pixbase[MW];
-#pragma unroll
-  for (int m = 0; m < MW; ++m) pixbase[m] = ((wave * MW + m) * a.tpw + col) * a.ccp;
-
-  for (int tile = walk.first; tile < walk.end; tile += walk.step) {
-    const int tx = ctx, ty = cty, nimg = cn;
-    advance(ctx, cty, cn);  // the next tile of this workgroup
-    const int ox0 = tx * TW, oy0 = ty * (NW * MW);
-    lds_barrier();  // previous tile's epilogue reads of the aliased region are done
-    {
-      int ty_ = x_ty0, tx_ = x_tx0, cg = x_cg0;
-#pragma unroll
-      for (int i = 0; i < PV; ++i) {
-        if (tid + NTHR * i < nvec_x) *(uint4*)(xs + (ty_ * a.tpw + tx_) * a.ccp + cg * 8) = pre[i];
-        cg += x_dc;
-        tx_ += x_dx;
-        ty_ += x_dy;
-        if (cg >= cvec) { cg -= cvec; ++tx_; }
-        if (tx_ >= a.tpw) { tx_ -= a.tpw; ++ty_; }
-      }
-    }
-    issue(tile + walk.step < walk.end, ctx, cty, cn);  // lands while this tile computes
-    lds_barrier();
-    f32x4 acc[MW][NT];
-#pragma unroll
-    for (int m = 0; m < MW; ++m)
-#pragma unroll
-      for (int t = 0; t < NT; ++t) acc[m][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    {
-      // k-steps two deep: k-step s+1's tap offset and fragments are read while s is on the MFMA pipe (one k-step at
-      // a time serialised tab read -> B read -> MFMAs, 3 lgkmcnt waits per 8 MFMAs)
-      if constexpr (GEO == 1) {
-        static_assert(NW * MW == 16, "GEO 1: 16-row tiles");
-        constexpr int TPW = TW + 2, CCP = 80, WP = 9 * 64 + WPAD;
-        const uint16_t* xb = xs + ((wave * MW) * TPW + col) * CCP + g * 8;
-        const uint16_t* wb = ws + col * WP + g * 8;
-        bf16x8 af[2][NT], bf[2][MW];
-        auto ldk = [&](int k, int b) {  // k-step k: tap k / 2, channels (k & 1) * 32 + 8 g
-          const int tap = k >> 1, off = ((tap / 3) * TPW + tap % 3) * CCP + (k & 1) * 32;
-#pragma unroll
-          for (int t = 0; t < NT; ++t) af[b][t] = *(const bf16x8*)(wb + t * 16 * WP + k * 32);
-#pragma unroll
-          for (int m = 0; m < MW; ++m) bf[b][m] = *(const bf16x8*)(xb + m * TPW * CCP + off);
-        };
-        ldk(0, 0);
-#pragma unroll
-        for (int k = 0; k < 18; ++k) {
-          if (k + 1 < 18) ldk(k + 1, (k + 1) & 1);
-          __builtin_amdgcn_sched_barrier(0);  // the next k-step's reads as one burst ahead of this k-step's MFMAs
-#pragma unroll
-          for (int m = 0; m < MW; ++m)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[k & 1][t], bf[k & 1][m], acc[m][t], 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      } else {
-      const int nks = a.kcpad / 32;
-      bf16x8 afA[NT], bfA[MW], afB[NT], bfB[MW];
-      auto ld = [&](int ks, bf16x8 (&af)[NT], bf16x8 (&bf)[MW]) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) af[t] = *(const bf16x8*)(ws + (t * 16 + col) * wpitch + ks * 32 + g * 8);
-        if constexpr (GEO == 2) {  // k values 8g..8g+7 of the step = taps 8 ks + 2g, +1, 4 channels each
-          const int off0 = tab[ks * 8 + 2 * g], off1 = tab[ks * 8 + 2 * g + 1];
-#pragma unroll
-          for (int m = 0; m < MW; ++m)
-            bf[m] = cat_tr(*(const s16x4*)(xs + pixbase[m] + off0), *(const s16x4*)(xs + pixbase[m] + off1));
-        } else {
-          const int off = tab[ks * 4 + g];
-#pragma unroll
-          for (int m = 0; m < MW; ++m) bf[m] = *(const bf16x8*)(xs + pixbase[m] + off);
-        }
-      };
-      auto mm = [&](const bf16x8 (&af)[NT], const bf16x8 (&bf)[MW]) {
-#pragma unroll
-        for (int m = 0; m < MW; ++m)
-#pragma unroll
-          for (int t = 0; t < NT; ++t) acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[t], bf[m], acc[m][t], 0, 0, 0);
-      };
-      ld(0, afA, bfA);
-      int ks = 0;
-      for (; ks + 2 <= nks; ks += 2) {
-        ld(ks + 1, afB, bfB);
-        mm(afA, bfA);
-        ld(ks + 2 < nks ? ks + 2 : nks - 1, afA, bfA);  // clamped: no branch around the reads
-        mm(afB, bfB);
-      }
-      if (ks < nks) mm(afA, bfA);
-      }
-    }
-    const int ox = ox0 + col;
-    if constexpr (EP == 5) {  // 2x2 sum + activation backward (act' of the bf16 low-res activation res1), bf16 out,
-                              // 4 channels (8 B) per lane; all operand loads issued before the first store
-      const int dh = a.out_h >> 1, dw = a.out_w >> 1;
-      const __amdgpu_buffer_rsrc_t rm1 = opt_rsrc(a.res1);
-      uint2 r1v[MW / 2][NT];
-#pragma unroll
-      for (int m = 0; m < MW; m += 2) {
-        const int oy = oy0 + wave * MW + m;
-        const bool ok = !(col & 1) && oy < a.out_h && ox < a.out_w;
-        const long q = ok ? ((long)nimg * dh + (oy >> 1)) * dw + (ox >> 1) : 0;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) r1v[m / 2][t] = buf_load8(rm1, (uint32_t)((q * a.r1_cs + (ok ? a.r1_co + t * 16 + g * 4 : 0)) * 2));
-      }
-#pragma unroll
-      for (int m = 0; m < MW; m += 2) {
-        const int oy = oy0 + wave * MW + m;
-        const long pidx = ((long)nimg * dh + (oy >> 1)) * dw + (ox >> 1);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          float v[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            float sm = acc[m][t][i] + acc[m + 1][t][i];
-            sm += __shfl_xor(sm, 1);
-            v[i] = sm;
-          }
-          if ((col & 1) || oy >= a.out_h || ox >= a.out_w) continue;
-          const uint4 r1 = make_uint4(r1v[m / 2][t].x, r1v[m / 2][t].y, 0, 0);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) v[i] = ep_res(v[i], a.act, a.slope, true, res4_at(r1, false, i), 1.f, 1.f, false, 0.f, 1.f, 1.f);
-          uint2 pk;
-          pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-          pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-          *(uint2*)((uint16_t*)a.y + pidx * a.out_cs + a.out_co + t * 16 + g * 4) = pk;
-        }
-      }
-      continue;
-    }
-    if (EP == 0 && a.down2) {  // 2x2 sum (data gradient of the nearest upsample): rows (m, m+1), columns via lane ^ 1
-      const int dh = a.out_h >> 1, dw = a.out_w >> 1;
-      const bool mask = a.act == 3 || a.act == 4;
-#pragma unroll
-      for (int m = 0; m < MW; m += 2) {
-        const int oy = oy0 + wave * MW + m;
-        const long pidx = ((long)nimg * dh + (oy >> 1)) * dw + (ox >> 1);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          float v[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            float sm = acc[m][t][i] + acc[m + 1][t][i];
-            sm += __shfl_xor(sm, 1);
-            v[i] = sm;
-          }
-          const int co = t * 16 + g * 4;
-          if ((col & 1) || oy >= a.out_h || ox >= a.out_w) continue;
-          const long ob = pidx * a.out_cs + a.out_co + co;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            if (co + i >= a.out_c) continue;
-            float x = v[i];
-            if (mask) x = ep_res(x, a.act, a.slope, true, res_at(a.res1, false, pidx * a.r1_cs + a.r1_co + co + i), 1.f, 1.f, false, 0.f,
-                                 1.f, 1.f);
-            if (a.out_mode == 0) ((uint16_t*)a.y)[ob + i] = f2bf(x);
-            else if (a.out_mode == 2) ((float*)a.y)[ob + i] += x;
-            else ((float*)a.y)[ob + i] = x;
-            if (a.aux) a.aux[pidx * a.aux_cs + a.aux_co + co + i] = f2bf(a.aux_scale * x);
-          }
-        }
-      }
-      continue;
-    }
-    constexpr int EPP = NT * 16 + 4;
-    float* eb = ebase + wave * (MW * 16 * EPP);
-    lds_barrier();  // all waves are done reading the input tile (the staging region aliases it)
-#pragma unroll
-    for (int m = 0; m < MW; ++m)
-#pragma unroll
-      for (int t = 0; t < NT; ++t) *(f32x4*)(eb + (m * 16 + col) * EPP + t * 16 + g * 4) = acc[m][t];
-    lds_barrier();
-    store_tile_lds<RF, MW * 16, NT * 16, 64, EP>(a, eb, EPP, lane, nimg, oy0 + wave * MW, ox0, 0);
-  }
-}
-
-template <int NW, int MW, int NT, int PV, int EP, int GEO>
-static int launch_pw_geo(const FwdArgs& a0, const PwGeom& g, hipStream_t s) {
-  if (g_dry) {
-    snprintf(g_dry_name, sizeof(g_dry_name), "conv_pw_kernel<%d, %d, %d, %s, %d, %d, %d>", NW, MW, NT, a0.res_f32 ? "true" : "false", PV, EP,
-             GEO);
-    return CLIMSR_OK;
-  }
-  FwdArgs a = a0;
-  a.tph = g.tph; a.tpw = g.tpw; a.ccp = g.ccp; a.kcpad = g.kcpad;
-  a.tiles_x = ceil_div(a.out_w, TW);
-  a.tiles_y = ceil_div(a.out_h, NW * MW);
-  a.lds_tab = (int)g.lds_tab;
-  a.lds_x = (int)g.lds_w;  // offset of the input tile = tab + weights
-  auto k = a.res_f32 ? conv_pw_kernel<NW, MW, NT, true, PV, EP, GEO> : conv_pw_kernel<NW, MW, NT, false, PV, EP, GEO>;
-  if (int e = lds_opt_in((const void*)k, 160 * 1024)) return e;
-  const int ncu = device_cus();
-  const int ntiles = a.tiles_x * a.tiles_y * a.n;
-  const int grid = ntiles < ncu ? ntiles : ncu;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(64 * NW), g.lds_total, s, a);
-  return check_launch("conv2d_fwd (pw)");
-}
-
-template <int NW, int MW, int NT, int PV, int EP = 0>
-static int launch_pw(const FwdArgs& a, const PwGeom& g, hipStream_t s) {
-  if (a.cc == 4) {  // 4-channel taps: staged as 8-channel pixels (16 B loads)
-    FwdArgs b = a;
-    b.cc = 8;
-    b.in_c = 8;
-    // one 16 B vector per pixel: the 24 x 24 (9x9) / 18 x 18 (3x3) input tile is <= 2 vectors per thread, and the
-    // staging loops run PV iterations of address math whether or not their vectors exist
-    if (g.nvx <= 2 * 64 * NW) return launch_pw_geo<NW, MW, NT, 2, EP, 2>(b, g, s);
-    return launch_pw_geo<NW, MW, NT, PV, EP, 2>(b, g, s);
-  }
-  if constexpr (NW * MW == 16) {
-    if (a.ks == 3 && a.cc == 64 && g.kcpad == 9 * 64 && g.ccp == 80 && g.tpw == TW + 2 && g.tph == 18)
-      return launch_pw_geo<NW, MW, NT, PV, EP, 1>(a, g, s);
-  }
-  return launch_pw_geo<NW, MW, NT, PV, EP, 0>(a, g, s);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1915,16 +1079,32 @@ __global__ __launch_bounds__(256) void dgrad_ci1_kernel(int n, int h, int w, int
   }
 }
 
+// the shape the data gradient takes (the operands are checked by the entry point), else the error set
+static bool dgrad_ci1_shape(int ks, int pad, int c, int act) {
+  if ((ks != 3 && ks != 5) || pad != ks / 2 || c <= 0 || c > 64 || c % 8 || (act != 0 && act != 3 && act != 4)) {
+    set_error("dgrad_single_output: unsupported arguments (ks %d pad %d c %d act %d)", ks, pad, c, act);
+    return false;
+  }
+  return true;
+}
+
+extern "C" const char* climsr_dgrad_single_output_kernel(int ks, int c, int act) {
+  static thread_local char name[96];
+  name[0] = 0;
+  if (dgrad_ci1_shape(ks, ks / 2, c, act)) snprintf(name, sizeof(name), "dgrad_ci1_kernel<%d, %d>", ks, c / 8);
+  return name;
+}
+
 extern "C" int climsr_dgrad_single_output(int n, int h, int w, int ks, int pad, const uint16_t* dz, int dz_cstride, int dz_coff,
                                           const float* weight, int c, int act, float slope, const uint16_t* res1, int res1_cstride,
                                           int res1_coff, uint16_t* out, int out_cstride, int out_coff, void* stream) {
-  if (!dz || !weight || !out || n <= 0 || h <= 0 || w <= 0 || (ks != 3 && ks != 5) || pad != ks / 2 || c <= 0 || c > 64 || c % 8 ||
-      (out_cstride | out_coff) % 8 || (act != 0 && act != 3 && act != 4) || (act && (!res1 || (res1_cstride | res1_coff) % 8))) {
+  if (!dz || !weight || !out || n <= 0 || h <= 0 || w <= 0 || (out_cstride | out_coff) % 8 ||
+      (act && (!res1 || (res1_cstride | res1_coff) % 8))) {
     set_error("dgrad_single_output: unsupported arguments (ks %d pad %d c %d act %d)", ks, pad, c, act);
     return CLIMSR_EINVAL;
   }
+  if (!dgrad_ci1_shape(ks, pad, c, act)) return CLIMSR_EINVAL;
   const long tiles = (long)n * ((h + S1_T - 1) / S1_T) * ((w + S1_T - 1) / S1_T);
-  if (dry_run("dgrad_ci1_kernel<%d, %d>", ks, c / 8)) return CLIMSR_OK;
 #define CLIMSR_CI1(KS_, LPP_)                                                                                              \
   hipLaunchKernelGGL((dgrad_ci1_kernel<KS_, LPP_>), dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, n, h, w, pad, dz, \
                      dz_cstride, dz_coff, weight, act, slope, res1, res1_cstride, res1_coff, out, out_cstride, out_coff)
@@ -1948,7 +1128,6 @@ extern "C" int climsr_conv_single_input(int n, int h, int w, int ks, int pad, co
     return CLIMSR_EINVAL;
   }
   const long tiles = (long)n * ((h + S1_T - 1) / S1_T) * ((w + S1_T - 1) / S1_T);
-  if (dry_run("dgrad_ci1_kernel<%d, %d, true>", ks, c / 8)) return CLIMSR_OK;
 #define CLIMSR_CI1F(KS_, LPP_)                                                                                                   \
   hipLaunchKernelGGL((dgrad_ci1_kernel<KS_, LPP_, true>), dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, n, h, w, pad, x, \
                      x_cstride, x_coff, weight, act, slope, nullptr, 0, 0, out, out_cstride, out_coff, bias)
@@ -1963,15 +1142,7 @@ extern "C" int climsr_conv_single_input(int n, int h, int w, int ks, int pad, co
 }
 
 template <int NCOF, int NKC>
-static int launch_pt(const FwdArgs& a, hipStream_t s) {
-  // epilogue specialisations: activation forward (3) / activation backward from a bf16 activation (4)
-  const bool plain = !a.res2 && !a.aux && a.out_mode == 0 && a.res_f32 == 0 && a.out_c == NCOF * 16;
-  const int ep = (plain && a.bias && !a.res1 && (a.act == 1 || a.act == 2)) ? 3
-                 : (plain && !a.bias && a.res1 && (a.act == 3 || a.act == 4)) ? 4 : 0;
-  if (g_dry) {
-    snprintf(g_dry_name, sizeof(g_dry_name), "conv_pt_kernel<%d, %d, %d>", NCOF, NKC, ep);
-    return CLIMSR_OK;
-  }
+static int launch_pt(int ep, const FwdArgs& a, hipStream_t s) {
   const long npix = (long)a.n * a.out_h * a.out_w;
   const long groups = (npix + 15) / 16;
   long blocks = (groups + 4 * PT_U - 1) / (4 * PT_U);
@@ -1982,20 +1153,10 @@ static int launch_pt(const FwdArgs& a, hipStream_t s) {
   return check_launch("conv2d_fwd (pt)");
 }
 
-static int dispatch_pt(const ClimsrConvDesc* d, const FwdArgs& a, hipStream_t s) {
-  const int ncof = (d->out_c + 15) / 16, nkc = d->in_c / 32;
-  switch (ncof * 10 + nkc) {
-    case 11: return launch_pt<1, 1>(a, s);
-    case 12: return launch_pt<1, 2>(a, s);
-    case 14: return launch_pt<1, 4>(a, s);
-    case 21: return launch_pt<2, 1>(a, s);
-    case 22: return launch_pt<2, 2>(a, s);
-    case 24: return launch_pt<2, 4>(a, s);
-    case 41: return launch_pt<4, 1>(a, s);
-    case 42: return launch_pt<4, 2>(a, s);
-    case 44: return launch_pt<4, 4>(a, s);
-    default: set_error("conv_pt: no instance for %d outputs / %d inputs", d->out_c, d->in_c); return CLIMSR_EINVAL;
-  }
+static int launch_co1(const FwdArgs& a, hipStream_t s) {
+  size_t lds = (size_t)(15 + a.ks) * (15 + a.ks) * (CO1_CC + 8) * 2 + (size_t)a.ks * a.ks * CO1_CC * 2;
+  hipLaunchKernelGGL(conv_co1_kernel, dim3(a.tiles_x * a.tiles_y * a.n), dim3(256), lds, s, a);
+  return check_launch("conv2d_fwd (co1)");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2245,27 +1406,39 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_s2_kernel(FwdArgs a) {
   }
 }
 
-static int plain_ep(const FwdArgs& a);
-static bool fwd_s2_shape(const ClimsrConvDesc* d, const FwdArgs& a) {
+template <int MW, int NT>
+static int launch_dgrad_s2_t(const FwdRoute& r, const FwdArgs& a, hipStream_t s) {
+  dim3 grid(ceil_div(a.tiles_x * a.tiles_y * a.n, 8) * 8 * (a.out_c / (NT * 16)));
+  const int lds = s2d_lds<MW>(NT);
+
+  if (r.ep == 4) hipLaunchKernelGGL((conv_dgrad_s2_kernel<4, MW, NT>), grid, dim3(256), lds, s, a);
+  else if (r.ep == 10) hipLaunchKernelGGL((conv_dgrad_s2_kernel<10, MW, NT>), grid, dim3(256), lds, s, a);
+  else hipLaunchKernelGGL((conv_dgrad_s2_kernel<0, MW, NT>), grid, dim3(256), lds, s, a);
+  return check_launch("conv2d_fwd (dgrad s2)");
+}
+
+// 2 x 4 (64 dx channels: whole 128 B pixel lines per workgroup) or 4 x 2, as the route chose
+static int launch_dgrad_s2(const FwdRoute& r, const FwdArgs& a, hipStream_t s) {
+  if (r.mw == 2) return launch_dgrad_s2_t<2, 4>(r, a, s);
+  return launch_dgrad_s2_t<4, 2>(r, a, s);
+}
+
+// Epilogue specialisations without residuals (store_tile_lds EP 3 / 6 / 7 / 8), or 0: activation forward with
+// (3) / without (6) bias, plain fp32 '=' output (7), plain bf16 output (8).  Needs 8-channel-aligned slices.
+static int plain_ep(const ClimsrConvDesc* d, bool bias, const ClimsrEpilogue* ep) {
+  if ((d->out_c & 7) || ((d->out_cstride | d->out_coff) & 7) || ep->down2 || ep->res1 || ep->res2 || ep->aux || ep->res_f32) return 0;
+  if (ep->out_mode == 0 && (ep->act == 1 || ep->act == 2)) return bias ? 3 : 6;
+  if (ep->act == 0 && !bias) return ep->out_mode == 1 ? 7 : ep->out_mode == 0 ? 8 : 0;
+  return 0;
+}
+
+static bool fwd_s2_shape(const ClimsrConvDesc* d, bool bias, const ClimsrEpilogue* ep, const FwdGeom& g) {
   return d->stride == 2 && d->ks == 3 && d->pad == 1 && d->up == 1 && d->cc == 32 && d->in_c % 32 == 0 && d->out_c % 64 == 0 &&
-         d->in_coff % 8 == 0 && d->in_cstride % 8 == 0 && a.kcpad == 288 && plain_ep(a) == 8 &&
+         d->in_coff % 8 == 0 && d->in_cstride % 8 == 0 && g.kcpad == 288 && plain_ep(d, bias, ep) == 8 &&
          (long)d->n * d->in_h * d->in_w * d->in_cstride * 2 < (1L << 31);  // the kernel's int / 32-bit input offsets
 }
 
-// the LDS-DMA kernel (conv_dma.hip conv_fwd_s2_dma_kernel); the register-staged 8-wave kernel it replaced measured
-// 352 against 332 us over the four discriminator stride-2 layers at B=32 (tools/perf_s2.py A/B, r04l)
-static int launch_fwd_s2(const ClimsrConvDesc* d, FwdArgs a, hipStream_t s) {
-  a.tiles_x = ceil_div(d->out_w, 16);
-  a.tiles_y = ceil_div(d->out_h, 16);
-  if (g_dry) {
-    snprintf(g_dry_name, sizeof(g_dry_name), "conv_fwd_s2_dma_kernel<%s>", a.bn_part ? "true" : "false");
-    return CLIMSR_OK;
-  }
-  const int rc = fwd_s2_dma_launch(a, s);
-  return rc == CLIMSR_OK ? check_launch("conv2d_fwd (s2 LDS-DMA)") : rc;
-}
-
-static bool dgrad_s2_shape(const ClimsrConvDesc* d, const ClimsrEpilogue* ep, const float* bias) {
+static bool dgrad_s2_shape(const ClimsrConvDesc* d, bool bias, const ClimsrEpilogue* ep) {
   const bool act_ok = ep->act == 0 ? !ep->res1 : ((ep->act == 3 || ep->act == 4) && ep->res1 && !(ep->res_f32 & 1) &&
                                                    ((ep->res1_cstride | ep->res1_coff) & 7) == 0);
   return d->up == -2 && d->stride == 1 && d->ks == 3 && d->pad == 1 && d->cc == 32 && d->in_c % 32 == 0 && d->out_c % 32 == 0 &&
@@ -2275,39 +1448,6 @@ static bool dgrad_s2_shape(const ClimsrConvDesc* d, const ClimsrEpilogue* ep, co
 
 // channel blocks grouped per tile in the XCD-major order: the largest divisor of ncob (>= 2) whose weight blocks
 // together stay within ~2.5 MB of the XCD's 4 MB L2 (they are re-read by every tile of the group), else 0
-// the second dispatch round of a two-workgroups-per-CU launch starts late (conv_fwd_body 'Stagger')
-static void set_stagger(FwdArgs& a) {
-  const int ncu = device_cus();
-  a.stag_lo = ncu;
-  a.stag_hi = 2 * ncu;
-  a.stag_n = 2;  // 2 x 2048 cycles: GAN step 25.25 -> 24.98 ms (same box, 2 + 6 runs)
-}
-
-template <int MW, int NT>
-static int launch_dgrad_s2_t(const ClimsrConvDesc* d, FwdArgs a, hipStream_t s) {
-  a.tiles_x = ceil_div(d->in_w, 16);
-  a.tiles_y = ceil_div(d->in_h, 4 * MW);
-  const bool ep4 = a.act == 3 || a.act == 4;
-  if (g_dry) {
-    snprintf(g_dry_name, sizeof(g_dry_name), "conv_dgrad_s2_kernel<%d, %d, %d>", ep4 ? 4 : a.bz ? 10 : 0, MW, NT);
-    return CLIMSR_OK;
-  }
-  dim3 grid(ceil_div(a.tiles_x * a.tiles_y * a.n, 8) * 8 * (d->out_c / (NT * 16)));
-  const int lds = s2d_lds<MW>(NT);
-
-  if (ep4) hipLaunchKernelGGL((conv_dgrad_s2_kernel<4, MW, NT>), grid, dim3(256), lds, s, a);
-  else if (a.bz) hipLaunchKernelGGL((conv_dgrad_s2_kernel<10, MW, NT>), grid, dim3(256), lds, s, a);
-  else hipLaunchKernelGGL((conv_dgrad_s2_kernel<0, MW, NT>), grid, dim3(256), lds, s, a);
-  return check_launch("conv2d_fwd (dgrad s2)");
-}
-
-static int launch_dgrad_s2(const ClimsrConvDesc* d, const FwdArgs& a, hipStream_t s) {
-  // 64 dx channels: one workgroup per 128 B pixel line (layer 1 with LeakyReLU': 158 -> 150 us at B=32; for wider
-  // layers the 4 x 2 form is 2-8 % faster)
-  if (d->out_c == 64) return launch_dgrad_s2_t<2, 4>(d, a, s);
-  return launch_dgrad_s2_t<4, 2>(d, a, s);
-}
-
 static int conv_xcd_group(int ncob, long wblk_bytes) {
   if (ncob < 2) return 0;
   for (int gsz = ncob; gsz >= 2; --gsz)
@@ -2315,149 +1455,186 @@ static int conv_xcd_group(int ncob, long wblk_bytes) {
   return 0;
 }
 
-// the LDS-DMA conv (conv_dma.hip)
-template <int EP>
-static int launch_fwd_dma(const FwdArgs& a0, int ncob, hipStream_t s) {
-  FwdArgs a = a0;
-  a.tiles_y = ceil_div(a.out_h, DMA_TH);
-  a.nchunk = a.in_c / 32;  // 32-channel chunks (of a 32- or 64-channel packing)
-  a.xgrp = conv_xcd_group(ncob, (long)64 * a.kpk * 2);
-  a.stag_n = 0;
-  if (g_dry) {
-    snprintf(g_dry_name, sizeof(g_dry_name), "conv_fwd_dma_kernel<%d, %s>", EP, a.res_f32 ? "true" : "false");
-    return CLIMSR_OK;
+// ------------------------------------------------------------------------------------------
+// The route
+// ------------------------------------------------------------------------------------------
+enum { PICK_OK = 0, PICK_CC4, PICK_LDS };  // fwd_pick: a kernel, or why the generic kernel cannot take the conv
+
+// the weights-resident persistent kernel for one-chunk convs with 17..64 outputs (large-pixel-count layers)
+static bool pick_pw(const ClimsrConvDesc* d, bool bias, const ClimsrEpilogue* ep, bool cc4, FwdRoute* r) {
+  const int nt = fwd_nt(d->out_c);
+  const long npx = (long)d->n * d->out_h * d->out_w;
+  if (!(r->ncob == 1 && (nt == 4 || nt == 2) && d->up != -2 && (npx >= 4096 || cc4) &&
+        (long)d->n * d->in_h * d->in_w * d->in_cstride * 2 < (1L << 31)))  // 32-bit buffer offsets
+    return false;
+  const bool al8 = (d->out_c & 7) == 0 && ((d->out_cstride | d->out_coff) & 7) == 0, r1 = ep->res1 != nullptr;
+  const bool r1al8 = ((ep->res1_cstride | ep->res1_coff) & 7) == 0, bwd = ep->act == 3 || ep->act == 4;
+  r->mw = 2; r->nt = nt;
+  // 8 waves x 2 rows (two waves per SIMD) when the LDS allows, else 4 waves x 2 rows
+  if (pw_geom(d, nt, 2, &r->pg, 8) && r->pg.nvx <= 512 * 7 && (d->out_h >= 16 || cc4)) {
+    // epilogue specialisations (store_tile_lds EP 3 / 4): activation forward / activation backward; 5: + down2
+    const bool v8 = al8 && !ep->down2 && !ep->res2 && !ep->aux && ep->out_mode == 0 && ep->res_f32 == 0;
+    const bool d2 = ep->down2 && d->out_c == 64 && ((d->out_cstride | d->out_coff) & 3) == 0 && !bias && r1 && ep->res_f32 == 0 &&
+                    ((ep->res1_cstride | ep->res1_coff) & 3) == 0 && bwd && !ep->res2 && !ep->aux && ep->out_mode == 0;
+    r->ep = (v8 && bias && !r1 && (ep->act == 1 || ep->act == 2)) ? 3 : (v8 && !bias && r1 && r1al8 && bwd) ? 4 : d2 ? 5 : 0;
+    const int plain = plain_ep(d, bias, ep);
+    if (nt == 4 && r->ep == 0 && plain >= 6) r->ep = plain;  // 6 / 7 / 8
+    r->nw = 8; r->pv = 7;
+  } else if (pw_geom(d, nt, 2, &r->pg, 4)) {
+    r->ep = 0; r->nw = 4; r->pv = 12;
+  } else {
+    return false;
   }
-  const int rc = fwd_dma_launch(EP, a, ncob, s);
-  return rc == CLIMSR_OK ? check_launch("conv2d_fwd (LDS-DMA)") : rc;
+  r->family = FAM_PW;
+  // 4-channel taps are staged as 8-channel pixels, one 16 B vector per pixel: the 24 x 24 (9x9) / 18 x 18 (3x3) input
+  // tile is <= 2 vectors per thread, and the staging loops run PV iterations of address math whether or not their
+  // vectors exist
+  if (d->cc == 4) {
+    r->geo = 2;
+    if (r->pg.nvx <= 2 * 64 * r->nw) r->pv = 2;
+  } else if (r->nw * r->mw == 16 && d->ks == 3 && d->cc == 64 && r->pg.kcpad == 9 * 64 && r->pg.ccp == 80 && r->pg.tpw == TW + 2 &&
+             r->pg.tph == 18) {
+    r->geo = 1;
+  }
+  r->tiles_y = ceil_div(d->out_h, r->nw * r->mw);
+  return true;
 }
 
-#define WIDE_GEO(pfx) ((pfx) == 18)
-template <int MW, int NT, int PFX, int PFW, int EP, int GEO>
-static int launch_fwd_geo(const FwdArgs& a0, int ncob, size_t lds, hipStream_t s) {
-  if constexpr (GEO == 1 && !WIDE_GEO(PFX) && MW == 4 && NT == 4) {
+// the generic kernel: tile shape and prefetch depth, epilogue, GEO form, and the LDS-DMA kernel where that takes over
+static void pick_generic(const ClimsrConvDesc* d, bool bias, const ClimsrEpilogue* ep, bool bz, FwdRoute* r) {
+  const FwdGeom& g = r->g;
+  const bool r1 = ep->res1 != nullptr, r2 = ep->res2 != nullptr, aux = ep->aux != nullptr, bwd = ep->act == 3 || ep->act == 4;
+  const bool al8 = (d->out_c & 7) == 0 && ((d->out_cstride | d->out_coff) & 7) == 0;
+  const bool r1al8 = ((ep->res1_cstride | ep->res1_coff) & 7) == 0;
+  const int plain = plain_ep(d, bias, ep);
+  r->family = FAM_FWD; r->mw = g.mw; r->nt = g.nt;
+  // (a stride-2 data gradient that only dgrad_s2's operand-size test turned away is still promised its partial rows)
+  r->parts = bz && d->up == -2 && plain == 8 && dgrad_s2_shape(d, bias, ep);
+  if (g.mw == 4) {
+    const int nrx = ceil_div(g.tph * g.tpw * (d->cc / 8), 256), nrw = ceil_div(g.nt * 16 * (g.kcpad / 8), 256);
+    r->nt = 4;
+    if (g.nchunk > 1 && nrx <= 6 && nrw <= 9) {
+      // multi-chunk tiles whose per-thread staging fits 6 input + 9 weight vectors: chunk-pipelined variant
+      r->pfx = 6; r->pfw = 9;
+      // epilogue specialisations (store_tile_lds EP): residual forward (conv5, trunk_conv) / fp32 pull-x
+      const bool v8 = al8 && r1al8 && (!r2 || ((ep->res2_cstride | ep->res2_coff) & 7) == 0) &&
+                      (!aux || ((ep->aux_cstride | ep->aux_coff) & 7) == 0) && !ep->down2 && ep->act == 0 && r1;
+      if (v8 && bias && ep->res_f32 == 0 && ep->out_mode == 0 && !aux) r->ep = 1;
+      else if (v8 && !bias && (ep->res_f32 & 1) && (!r2 || (ep->res_f32 & 2)) && ep->out_mode == 1) r->ep = 2;
+      // activation backward from a bf16 activation, bf16 out (the discriminator's layer-1 data gradient)
+      else if (!bias && r1 && bwd && ep->res_f32 == 0 && !r2 && !aux && !ep->down2 && ep->out_mode == 0 && al8 && r1al8) r->ep = 4;
+      else if (plain == 8) r->ep = bz ? 10 : ep->bn_part ? 9 : 8;
+      else r->ep = plain;  // 3 / 6 / 7, or 0
+      // BatchNorm partials per 16x16 tile of 64-channel blocks, >= 2 blocks (one block is conv_pw's or conv_n16's)
+      r->parts |= (r->ep == 9 || r->ep == 10) && d->out_c % 64 == 0 && d->out_c >= 128 && d->stride == 1 && d->up == 1 && d->ks == 3;
+    } else if (g.nchunk > 1 && nrx <= 18 && nrw <= 9) {
+      // large input tiles (stride 2: 33x33 pixels per 16x16 outputs) with several chunks: the deeper-prefetch
+      // variant (one workgroup per CU already, so the 18 staging vectors per thread cost no occupancy)
+      r->pfx = 18; r->pfw = 9; r->ep = plain == 8 ? 8 : 0;
+    } else {
+      r->ep = plain;
+    }
+    // the GEO specialisation matching the geometry (conv_fwd_kernel): 16x16 tiles of 3x3 taps over 32-channel chunks
+    const bool base = d->cc == 32 && d->ks == 3 && g.kcpad == 9 * 32;
+    if (r->pfx != 18 && base && d->stride == 1 && g.tpw == TW + 2 && g.ccp == 48 && d->up == 1 && d->in_c % 32 == 0 &&
+        g.nchunk * 32 == d->in_c && (long)d->n * d->in_h * d->in_w * d->in_cstride * 2 < (1L << 31) &&
+        (long)r->ncob * r->nt * 16 * g.kpk * 2 < (1L << 31))
+      r->geo = 1;
+    if (r->pfx == 18 && base && d->stride == 2 && g.tpw == 2 * TW + 1 && g.ccp == 40) r->geo = 2;
+  }
+  if (r->geo == 1) {
     // the LDS-DMA form for the tiles it fills (32-row tiles: not the 16^2 VGG conv5 layers); with BatchNorm partials
     // (per 16 x 16 tile) only when every 32-row tile holds two whole 16-row tiles
     // RDB conv5 / pull-x (EP 1 / 2: 256 items at B=32 64^2, one round of one workgroup per CU) measured 7 % slower in
     // the GAN step than the two-workgroups-per-CU form (its chunk-0 latency and epilogue are not hidden in a single
     // round)
-    const bool fits = (EP == 9 || EP == 10) ? a0.out_h % DMA_TH == 0 : (a0.out_h % DMA_TH == 0 || a0.out_h >= 3 * DMA_TH);
-    if (EP != 1 && EP != 2 && !a0.down2 && fits) return launch_fwd_dma<EP>(a0, ncob, s);
+    const bool fits = (r->ep == 9 || r->ep == 10) ? d->out_h % DMA_TH == 0 : (d->out_h % DMA_TH == 0 || d->out_h >= 3 * DMA_TH);
+    if (r->ep != 1 && r->ep != 2 && !ep->down2 && fits) {
+      r->family = FAM_DMA;
+      r->tiles_y = ceil_div(d->out_h, DMA_TH);
+      r->xgrp = conv_xcd_group(r->ncob, (long)64 * g.kpk * 2);
+      return;
+    }
+    r->xgrp = conv_xcd_group(r->ncob, (long)r->nt * 16 * g.kpk * 2);
   }
-  FwdArgs a = a0;
-  a.xgrp = GEO == 1 ? conv_xcd_group(ncob, (long)NT * 16 * a.kpk * 2) : 0;
-  set_stagger(a);
-  if (GEO != 1 || WIDE_GEO(PFX)) a.stag_n = 0;
-  const dim3 grid = a.xgrp ? dim3(a.tiles_x * a.tiles_y * a.n * ncob) : dim3(a.tiles_x * a.tiles_y * a.n, ncob);
-  const size_t lds_ep = (size_t)4 * MW * 16 * (NT * 16 + 4) * 4;  // epilogue staging (aliases the operands)
-  if (lds_ep > lds) lds = lds_ep;
-  constexpr int MV = NT == 1 ? 6 : (NT == 2 ? 8 : 4);
-  constexpr bool WIDE = PFX == 18;
-  if (g_dry) {
-    snprintf(g_dry_name, sizeof(g_dry_name), "%s<%d, %d, %s, %d, %d, %d, %d, %d>", WIDE ? "conv_fwd_wide_kernel" : "conv_fwd_kernel", MW, NT,
-             a.res_f32 ? "true" : "false", MV, PFX, PFW, EP, GEO);
-    return CLIMSR_OK;
-  }
-  void (*kt)(FwdArgs);
-  void (*kf)(FwdArgs);
-  if constexpr (WIDE) {
-    kt = conv_fwd_wide_kernel<MW, NT, true, MV, PFX, PFW, EP, GEO>;
-    kf = conv_fwd_wide_kernel<MW, NT, false, MV, PFX, PFW, EP, GEO>;
-  } else {
-    kt = conv_fwd_kernel<MW, NT, true, MV, PFX, PFW, EP, GEO>;
-    kf = conv_fwd_kernel<MW, NT, false, MV, PFX, PFW, EP, GEO>;
-  }
-  auto k = a.res_f32 ? kt : kf;
-  if (int e = lds_opt_in((const void*)k, 160 * 1024)) return e;
-  hipLaunchKernelGGL(k, grid, dim3(256), lds, s, a);
-  return check_launch("conv2d_fwd");
+  const size_t lds_ep = (size_t)4 * r->mw * 16 * (r->nt * 16 + 4) * 4;  // epilogue staging (aliases the operands)
+  r->lds = lds_ep > g.lds_total ? lds_ep : g.lds_total;
 }
 
-// the GEO specialisation matching a's geometry (conv_fwd_kernel): 16x16 tiles of 3x3 taps over 32-channel chunks
-template <int MW, int NT, int PFX = 0, int PFW = 0, int EP = 0>
-static int launch_fwd_ep(const FwdArgs& a, int ncob, size_t lds, hipStream_t s) {
-  const bool base = MW == 4 && a.cc == 32 && a.ks == 3 && a.kcpad == 9 * 32;
-  if constexpr (MW == 4 && PFX != 18) {
-    if (base && a.stride == 1 && a.tpw == TW + 2 && a.ccp == 48 && a.up == 1 && a.in_c % 32 == 0 && a.nchunk * 32 == a.in_c &&
-        (long)a.n * a.in_h * a.in_w * a.in_cs * 2 < (1L << 31) && (long)ncob * NT * 16 * a.kpk * 2 < (1L << 31))
-      return launch_fwd_geo<MW, NT, PFX, PFW, EP, 1>(a, ncob, lds, s);
-  }
-  if constexpr (MW == 4 && PFX == 18) {
-    if (base && a.stride == 2 && a.tpw == 2 * TW + 1 && a.ccp == 40) return launch_fwd_geo<MW, NT, PFX, PFW, EP, 2>(a, ncob, lds, s);
-  }
-  return launch_fwd_geo<MW, NT, PFX, PFW, EP, 0>(a, ncob, lds, s);
-}
-
-template <int MW, int NT, int PFX = 0, int PFW = 0>
-static int launch_fwd(const FwdArgs& a, int ncob, size_t lds, hipStream_t s) {
-  return launch_fwd_ep<MW, NT, PFX, PFW, 0>(a, ncob, lds, s);
-}
-
-
-// Epilogue specialisations without residuals (store_tile_lds EP 3 / 6 / 7 / 8), or 0: activation forward with
-// (3) / without (6) bias, plain fp32 '=' output (7), plain bf16 output (8).  Needs 8-channel-aligned slices.
-static int plain_ep(const FwdArgs& a) {
-  if ((a.out_c & 7) || ((a.out_cs | a.out_co) & 7) || a.down2 || a.res1 || a.res2 || a.aux || a.res_f32) return 0;
-  if (a.out_mode == 0 && (a.act == 1 || a.act == 2)) return a.bias ? 3 : 6;
-  if (a.act == 0 && !a.bias) return a.out_mode == 1 ? 7 : a.out_mode == 0 ? 8 : 0;
-  return 0;
-}
-
-// The convs whose epilogue can emit BatchNorm partials (EP 9 / conv_fwd_s2_dma_kernel<true>): plain bf16 out over 16x16
-// tiles of 64-channel blocks -- the stride-2 kernel, or the chunk-pipelined generic kernel with >= 2 channel blocks
-// (so neither conv_pw nor conv_n16 takes it).  Mirrors the dispatch below.
-static bool bn_parts_ok(const ClimsrConvDesc* d, const FwdArgs& a, const FwdGeom& g) {
-  if (plain_ep(a) != 8 || d->out_c % 64) return false;
-  if (d->stride == 2) return fwd_s2_shape(d, a);
-  const int nrx = ceil_div(g.tph * g.tpw * (d->cc / 8), 256), nrw = ceil_div(g.nt * 16 * (g.kcpad / 8), 256);
-  return d->stride == 1 && d->up == 1 && d->ks == 3 && g.mw == 4 && g.nt == 4 && d->out_c >= 128 && g.nchunk > 1 && nrx <= 6 &&
-         nrw <= 9 && g.lds_total <= 160 * 1024;
-}
-
-// Backward partials (ep->bn_z): the stride-1 16x16-tile path (EP 10) or the phase-decomposed stride-2 data gradient
-static bool bn_bwd_parts_ok(const ClimsrConvDesc* d, const ClimsrEpilogue* ep, const FwdArgs& a, const FwdGeom& g) {
-  if (plain_ep(a) != 8) return false;
-  if (d->up == -2) return dgrad_s2_shape(d, ep, nullptr);
-  return d->stride == 1 && bn_parts_ok(d, a, g);
-}
-
-extern "C" int climsr_conv2d_fwd(const ClimsrConvDesc* d, const uint16_t* x, const uint16_t* wpk, const float* bias,
-                                 const ClimsrEpilogue* ep, void* y, void* stream);
-namespace climsr {
-int conv_wr_launch(const ClimsrConvDesc* d, const ClimsrEpilogue* ep, const uint16_t* x, const uint16_t* wpk, int kpk,
-                   const float* bias, void* y, hipStream_t s, bool dry, char* name, int name_len);
-long conv_wr_ch_parts(const ClimsrConvDesc* d, const ClimsrEpilogue* ep, int* tiles_per_image);
-int conv_wr_ep(const ClimsrConvDesc* d, const ClimsrEpilogue* ep, const float* bias);
-}
-
-extern "C" int64_t climsr_conv2d_fwd_ch_parts(const ClimsrConvDesc* d, const ClimsrEpilogue* ep, int32_t* tiles_per_image) {
-  if (!d || !ep) return 0;
-  return conv_wr_ch_parts(d, ep, tiles_per_image);
-}
-
-extern "C" int64_t climsr_conv2d_fwd_bn_parts(const ClimsrConvDesc* d, const ClimsrEpilogue* ep) {
-  if (!d || !ep || d->cc % 8 || d->cc <= 0 || d->stride < 1) return 0;
+// The kernel of (d, bias, ep): the families in the order they claim a conv.  d->cc > 0.
+static int fwd_pick(const ClimsrConvDesc* d, bool bias, const ClimsrEpilogue* ep, FwdRoute* r) {
+  *r = FwdRoute{};
+  const bool cc4 = d->cc == 4 && d->in_c == 4;  // conv_pw GEO 2 (climsr_conv_chunk_ex)
+  const bool bz = ep->bn_part && ep->bn_z, r1 = ep->res1 != nullptr, r2 = ep->res2 != nullptr, aux = ep->aux != nullptr;
+  FwdGeom& g = r->g;
+  // 16x16 output tiles (64 px per wave) for the 64-channel layers; 8x16 otherwise
   const int mw = (d->out_h >= 12 && fwd_nt(d->out_c) == 4) ? 4 : 2;
-  FwdGeom g;
   fwd_geom(d->in_c, d->ks, d->stride, d->out_c, d->cc, mw, &g);
-  FwdArgs a{};
-  a.act = ep->act; a.out_mode = ep->out_mode; a.down2 = ep->down2; a.res1 = ep->res1; a.res2 = ep->res2; a.aux = (uint16_t*)ep->aux;
-  a.res_f32 = ep->res_f32; a.out_c = d->out_c; a.out_cs = d->out_cstride; a.out_co = d->out_coff; a.kcpad = g.kcpad;
-  if (ep->bn_z) {
-    if (!bn_bwd_parts_ok(d, ep, a, g)) return 0;
-    if (d->up == -2) return (int64_t)ceil_div(d->in_w, 16) * ceil_div(d->in_h, 4 * (d->out_c == 64 ? 2 : 4)) * d->n;  // dz tiles
-    return (int64_t)ceil_div(d->out_w, TW) * ceil_div(d->out_h, 16) * d->n;
+  r->ncob = g.nt ? round_up(d->out_c, g.nt * 16) / (g.nt * 16) : 0;  // (the queries pick for unchecked descriptors)
+  r->rf = ep->res_f32 != 0;
+  r->tiles_x = ceil_div(d->out_w, TW); r->tiles_y = ceil_div(d->out_h, g.th);
+  if (d->out_c == 1 && d->stride == 1 && d->up == 1 && !ep->down2 && !r2) {
+    if (co1m_shape(d)) {
+      r->family = FAM_CO1M; r->ks = d->ks; r->nch = d->in_c <= 32 ? 1 : 2;
+    } else {
+      r->family = FAM_CO1; r->tiles_x = ceil_div(d->out_w, 16); r->tiles_y = ceil_div(d->out_h, 16);
+    }
+    return PICK_OK;
   }
-  if (!bn_parts_ok(d, a, g)) return 0;
-  return (int64_t)ceil_div(d->out_w, TW) * ceil_div(d->out_h, 16) * d->n;
+  if (n16_shape(d->in_c, d->ks, d->out_c) && d->cc == 32 * n16_ncb(d->in_c) && d->stride == 1 && d->up == 1 && d->pad == 1 &&
+      !ep->down2 && !ep->res_f32 && d->out_h == d->in_h && d->out_w == d->in_w &&
+      (long)d->n * d->in_h * d->in_w * d->in_cstride * 2 < (1L << 31)) {  // 32-bit buffer offsets
+    // epilogue specialisations (see conv_n16_kernel): forward conv1-4 and the pull data gradients
+    const bool al = ((d->out_cstride | d->out_coff) & 3) == 0 && d->out_c == 16 && !r2 && !aux && ep->out_mode == 0;
+    r->family = FAM_N16; r->nch = d->cc / 32; r->tiles_y = ceil_div(d->out_h, N16_TH);
+    r->ep = (al && ep->act == 1 && bias && !r1) ? 1
+            : (al && ep->act == 3 && !bias && r1 && !(ep->res_f32 & 1) && ((ep->res1_cstride | ep->res1_coff) & 3) == 0) ? 2 : 0;
+    return PICK_OK;
+  }
+  if (dgrad_s2_shape(d, bias, ep) && (long)d->n * d->out_h * d->out_w * ep->res1_cstride * 2 < (1L << 32) - 64) {
+    r->family = FAM_DGRAD_S2;
+    r->ep = (ep->act == 3 || ep->act == 4) ? 4 : bz ? 10 : 0;
+    // 64 dx channels: one workgroup per 128 B pixel line (layer 1 with LeakyReLU': 158 -> 150 us at B=32; for wider
+    // layers the 4 x 2 form is 2-8 % faster)
+    r->mw = d->out_c == 64 ? 2 : 4; r->nt = d->out_c == 64 ? 4 : 2;
+    r->tiles_x = ceil_div(d->in_w, 16); r->tiles_y = ceil_div(d->in_h, 4 * r->mw);
+    r->parts = r->ep == 10 && plain_ep(d, bias, ep) == 8;
+    return PICK_OK;
+  }
+  // the LDS-DMA kernel (conv_dma.hip conv_fwd_s2_dma_kernel); the register-staged 8-wave kernel it replaced measured
+  // 352 against 332 us over the four discriminator stride-2 layers at B=32 (tools/perf_s2.py A/B, r04l)
+  if (fwd_s2_shape(d, bias, ep, g)) {
+    r->family = FAM_FWD_S2; r->ep = ep->bn_part ? 9 : 8;
+    r->tiles_x = ceil_div(d->out_w, 16); r->tiles_y = ceil_div(d->out_h, 16);
+    r->parts = ep->bn_part && !ep->bn_z;
+    return PICK_OK;
+  }
+  if (pt_shape(d, ep) && (d->out_c == 16 || d->out_c == 32 || d->out_c == 64) && (d->in_c == 32 || d->in_c == 64 || d->in_c == 128)) {
+    // epilogue specialisations: activation forward (3) / activation backward from a bf16 activation (4)
+    const bool plain = !r2 && !aux && ep->out_mode == 0 && ep->res_f32 == 0;
+    r->family = FAM_PT; r->nt = d->out_c / 16; r->nch = d->in_c / 32;
+    r->ep = (plain && bias && !r1 && (ep->act == 1 || ep->act == 2)) ? 3 : (plain && !bias && r1 && (ep->act == 3 || ep->act == 4)) ? 4 : 0;
+    return PICK_OK;
+  }
+  // 64 -> 64 3x3: the weights resident in registers, wave-independent tiles (conv_wr.hip)
+  if (const int epk = conv_wr_ep(d, ep, bias); epk >= 0 && g.kpk >= 576) {
+    r->family = FAM_WR; r->ep = epk;
+    return PICK_OK;
+  }
+  if (pick_pw(d, bias, ep, cc4, r)) return PICK_OK;
+  if (cc4) return PICK_CC4;
+  if (g.lds_total > 160 * 1024) return PICK_LDS;
+  pick_generic(d, bias, ep, bz, r);
+  return PICK_OK;
 }
 
-extern "C" int climsr_conv2d_fwd(const ClimsrConvDesc* d, const uint16_t* x, const uint16_t* wpk, const float* bias,
-                                 const ClimsrEpilogue* ep, void* y, void* stream) {
-  if (!d || !x || !wpk || !ep || !y) {
+// fwd_pick behind the argument checks of climsr_conv2d_fwd, in the order it reports them
+static int fwd_route(const ClimsrConvDesc* d, bool bias, const ClimsrEpilogue* ep, FwdRoute* r) {
+  if (!d || !ep) {
     set_error("conv2d_fwd: null argument");
     return CLIMSR_EINVAL;
   }
-  const bool cc4 = d->cc == 4 && d->in_c == 4;  // conv_pw GEO 2 (climsr_conv_chunk_ex)
+  const bool cc4 = d->cc == 4 && d->in_c == 4;
   if ((d->in_c % 8 && !cc4) || d->in_cstride % 8 || d->in_coff % 8 || (d->cc % 8 && !cc4) || d->cc <= 0 ||
       (d->up != 1 && d->up != 2 && d->up != -2) ||
       (d->stride != 1 && d->stride != 2) || d->ks < 1 || d->n <= 0 || d->out_c <= 0 || d->in_coff + d->in_c > d->in_cstride) {
@@ -2474,7 +1651,8 @@ extern "C" int climsr_conv2d_fwd(const ClimsrConvDesc* d, const uint16_t* x, con
     set_error("conv2d_fwd: act %d invalid (3/4 need res1 = the activation output)", ep->act);
     return CLIMSR_EINVAL;
   }
-  if (ep->ch_part && conv_wr_ep(d, ep, bias) != 3 && conv_wr_ep(d, ep, bias) != 4) {
+  const int pick = fwd_pick(d, bias, ep, r);
+  if (ep->ch_part && !(pick == PICK_OK && r->family == FAM_WR && (r->ep == 3 || r->ep == 4))) {
     set_error("conv2d_fwd: per-tile channel sums only from the 64 -> 64 3x3 register-resident conv "
               "(climsr_conv2d_fwd_ch_parts)");
     return CLIMSR_EINVAL;
@@ -2494,11 +1672,51 @@ extern "C" int climsr_conv2d_fwd(const ClimsrConvDesc* d, const uint16_t* x, con
       return CLIMSR_EINVAL;
     }
   }
-  FwdGeom g;
-  // 16x16 output tiles (64 px per wave) for the 64-channel layers; 8x16 otherwise
-  const int mw = (d->out_h >= 12 && fwd_nt(d->out_c) == 4) ? 4 : 2;
-  fwd_geom(d->in_c, d->ks, d->stride, d->out_c, d->cc, mw, &g);
-  FwdArgs a{};  // zero: the optional operands (bz, bn_part, xgrp, ...) default to absent
+  if (ep->bn_part && ep->bn_z &&
+      (!ep->bn_mean || !ep->bn_rstd || !ep->bn_gamma || !ep->bn_beta || ep->bn_z_cstride < d->out_c || ep->bn_z_cstride % 8 ||
+       (long)d->n * d->out_h * d->out_w * ep->bn_z_cstride * 2 >= (1L << 31))) {
+    set_error("conv2d_fwd: BatchNorm-backward partials need z (channel stride >= out_c, 8-aligned, < 2 GiB) and its statistics");
+    return CLIMSR_EINVAL;
+  }
+  if (ep->bn_part && !(pick == PICK_OK && r->parts)) {
+    set_error("conv2d_fwd: BatchNorm partials only for the 16x16-tile bf16 paths (climsr_conv2d_fwd_bn_parts)");
+    return CLIMSR_EINVAL;
+  }
+  if (pick == PICK_CC4) {
+    set_error("conv2d_fwd: 4-channel chunks need the conv_pw path (stride 1, up 1/2, 64 outputs, 32-bit offsets)");
+    return CLIMSR_EINVAL;
+  }
+  if (pick == PICK_LDS) {
+    set_error("conv2d_fwd: LDS %zu exceeds 160 KiB (cc=%d)", r->g.lds_total, d->cc);
+    return CLIMSR_EINVAL;
+  }
+  return CLIMSR_OK;
+}
+
+// the kernel's name as rocprof reports it
+static void fwd_route_name(const FwdRoute& r, char* name, size_t len) {
+  const char* rf = r.rf ? "true" : "false";
+  switch (r.family) {
+    case FAM_CO1M: snprintf(name, len, "conv_co1m_kernel<%d, %d>", r.ks, r.nch); break;
+    case FAM_CO1: snprintf(name, len, "conv_co1_kernel"); break;
+    case FAM_N16: snprintf(name, len, "conv_n16_kernel<%d, %d>", r.nch, r.ep); break;
+    case FAM_DGRAD_S2: snprintf(name, len, "conv_dgrad_s2_kernel<%d, %d, %d>", r.ep, r.mw, r.nt); break;
+    case FAM_FWD_S2: snprintf(name, len, "conv_fwd_s2_dma_kernel<%s>", r.ep == 9 ? "true" : "false"); break;
+    case FAM_PT: snprintf(name, len, "conv_pt_kernel<%d, %d, %d>", r.nt, r.nch, r.ep); break;
+    case FAM_WR: snprintf(name, len, "conv_wr_kernel<%d>", r.ep); break;
+    case FAM_PW: snprintf(name, len, "conv_pw_kernel<%d, %d, %d, %s, %d, %d, %d>", r.nw, r.mw, r.nt, rf, r.pv, r.ep, r.geo); break;
+    case FAM_DMA: snprintf(name, len, "conv_fwd_dma_kernel<%d, %s>", r.ep, rf); break;
+    default:
+      snprintf(name, len, "%s<%d, %d, %s, %d, %d, %d, %d, %d>", r.pfx == 18 ? "conv_fwd_wide_kernel" : "conv_fwd_kernel", r.mw, r.nt,
+               rf, fwd_mv(r.nt), r.pfx, r.pfw, r.ep, r.geo);
+  }
+}
+
+// the kernel arguments of route r
+static FwdArgs fwd_args(const FwdRoute& r, const ClimsrConvDesc* d, const uint16_t* x, const uint16_t* wpk, const float* bias,
+                        const ClimsrEpilogue* ep, void* y) {
+  const FwdGeom& g = r.g;
+  FwdArgs a{};  // zero: the optional operands (bz, bn_part, the stagger, ...) default to absent
   a.x = x; a.w = wpk; a.bias = bias; a.y = y;
   a.res1 = ep->res1; a.res2 = ep->res2; a.aux = (uint16_t*)ep->aux;
   a.res_f32 = ep->res_f32; a.beta1 = ep->beta1; a.beta2 = ep->beta2;
@@ -2507,182 +1725,98 @@ extern "C" int climsr_conv2d_fwd(const ClimsrConvDesc* d, const uint16_t* x, con
   a.up = d->up; a.ks = d->ks; a.stride = d->stride; a.pad = d->pad; a.out_h = d->out_h; a.out_w = d->out_w;
   a.out_c = d->out_c; a.out_cs = d->out_cstride; a.out_co = d->out_coff; a.cc = d->cc;
   a.tph = g.tph; a.tpw = g.tpw; a.ccp = g.ccp; a.kcpad = g.kcpad; a.nchunk = g.nchunk; a.kpk = g.kpk;
-  a.tiles_x = ceil_div(d->out_w, TW); a.tiles_y = ceil_div(d->out_h, g.th);
+  a.tiles_x = r.tiles_x; a.tiles_y = r.tiles_y;
   a.act = ep->act; a.out_mode = ep->out_mode; a.down2 = ep->down2;
   a.slope = ep->slope; a.alpha1 = ep->alpha1; a.alpha2 = ep->alpha2;
   a.r1_cs = ep->res1_cstride; a.r1_co = ep->res1_coff; a.r2_cs = ep->res2_cstride; a.r2_co = ep->res2_coff;
   a.lds_tab = (int)g.lds_tab; a.lds_x = (int)g.lds_x;
   a.bn_part = ep->bn_part;
+  a.xgrp = r.xgrp;
   if (ep->bn_part && ep->bn_z) {
-    if (!ep->bn_mean || !ep->bn_rstd || !ep->bn_gamma || !ep->bn_beta || ep->bn_z_cstride < d->out_c || ep->bn_z_cstride % 8 ||
-        (long)d->n * d->out_h * d->out_w * ep->bn_z_cstride * 2 >= (1L << 31)) {
-      set_error("conv2d_fwd: BatchNorm-backward partials need z (channel stride >= out_c, 8-aligned, < 2 GiB) and its statistics");
-      return CLIMSR_EINVAL;
-    }
     a.bz = ep->bn_z; a.bz_cs = ep->bn_z_cstride; a.bslope = ep->bn_slope;
     a.bmean = ep->bn_mean; a.brstd = ep->bn_rstd; a.bgamma = ep->bn_gamma; a.bbeta = ep->bn_beta;
   }
-  int rows = climsr_conv_packed_rows(d->out_c);
-  int ncob = rows / (g.nt * 16);
+  if (r.family == FAM_PW) {
+    const PwGeom& p = r.pg;
+    a.tph = p.tph; a.tpw = p.tpw; a.ccp = p.ccp; a.kcpad = p.kcpad;
+    a.lds_tab = (int)p.lds_tab;
+    a.lds_x = (int)p.lds_w;  // offset of the input tile = tab + weights
+    if (d->cc == 4) a.cc = a.in_c = 8;  // 4-channel taps: staged as 8-channel pixels (16 B loads)
+  }
+  if (r.family == FAM_DMA) a.nchunk = a.in_c / 32;  // 32-channel chunks (of a 32- or 64-channel packing)
+  return a;
+}
+
+// CO1M, CO1, N16, PT: the instantiation of the route's ids
+static int launch_small(const FwdRoute& r, const FwdArgs& a, hipStream_t s) {
+  if (r.family == FAM_CO1) return launch_co1(a, s);
+#define CO1M_CASE(KS, NCH) \
+  if (r.family == FAM_CO1M && r.ks == KS && r.nch == NCH) return launch_co1m<KS, NCH>(a, s);
+#define N16_CASE(NCB, EP) \
+  if (r.family == FAM_N16 && r.nch == NCB && r.ep == EP) return launch_n16<NCB, EP>(a, s);
+#define PT_CASE(NCOF, NKC) \
+  if (r.family == FAM_PT && r.nt == NCOF && r.nch == NKC) return launch_pt<NCOF, NKC>(r.ep, a, s);
+  CO1M_CASE(3, 1) CO1M_CASE(3, 2) CO1M_CASE(5, 1) CO1M_CASE(5, 2) CO1M_CASE(9, 1) CO1M_CASE(9, 2)
+  N16_CASE(1, 0) N16_CASE(1, 1) N16_CASE(1, 2) N16_CASE(2, 0) N16_CASE(2, 1) N16_CASE(2, 2) N16_CASE(4, 0) N16_CASE(4, 1) N16_CASE(4, 2)
+  PT_CASE(1, 1) PT_CASE(1, 2) PT_CASE(1, 4) PT_CASE(2, 1) PT_CASE(2, 2) PT_CASE(2, 4) PT_CASE(4, 1) PT_CASE(4, 2) PT_CASE(4, 4)
+#undef CO1M_CASE
+#undef N16_CASE
+#undef PT_CASE
+  set_error("conv2d_fwd: no small-shape kernel for family %d (ks %d, nch %d, nt %d, ep %d)", r.family, r.ks, r.nch, r.nt, r.ep);
+  return CLIMSR_EINVAL;
+}
+
+extern "C" int climsr_conv2d_fwd(const ClimsrConvDesc* d, const uint16_t* x, const uint16_t* wpk, const float* bias,
+                                 const ClimsrEpilogue* ep, void* y, void* stream) {
+  if (!d || !x || !wpk || !ep || !y) {
+    set_error("conv2d_fwd: null argument");
+    return CLIMSR_EINVAL;
+  }
+  FwdRoute r;
+  if (int e = fwd_route(d, bias != nullptr, ep, &r)) return e;
   hipStream_t s = (hipStream_t)stream;
-  if (ep->bn_part && !(ep->bn_z ? bn_bwd_parts_ok(d, ep, a, g) : bn_parts_ok(d, a, g))) {
-    set_error("conv2d_fwd: BatchNorm partials only for the 16x16-tile bf16 paths (climsr_conv2d_fwd_bn_parts)");
-    return CLIMSR_EINVAL;
-  }
-  if (d->out_c == 1 && d->stride == 1 && d->up == 1 && !ep->down2 && !ep->res2 && co1m_shape(d))
-    return dispatch_co1m(d, a, s);
-  if (d->out_c == 1 && d->stride == 1 && d->up == 1 && !ep->down2 && !ep->res2) {
-    a.tiles_x = ceil_div(d->out_w, 16);
-    a.tiles_y = ceil_div(d->out_h, 16);
-    size_t lds = (size_t)(15 + d->ks) * (15 + d->ks) * (CO1_CC + 8) * 2 + (size_t)d->ks * d->ks * CO1_CC * 2;
-    if (g_dry) {
-      snprintf(g_dry_name, sizeof(g_dry_name), "conv_co1_kernel");
-      return CLIMSR_OK;
+  if (r.family == FAM_WR) return conv_wr_launch(r.ep, d, ep, x, wpk, r.g.kpk, bias, y, s);
+  const FwdArgs a = fwd_args(r, d, x, wpk, bias, ep, y);
+  switch (r.family) {
+    case FAM_PW: return fwd_pw_launch(r, a, s);
+    case FAM_DGRAD_S2: return launch_dgrad_s2(r, a, s);
+    case FAM_FWD_S2: {
+      const int rc = fwd_s2_dma_launch(a, s);
+      return rc == CLIMSR_OK ? check_launch("conv2d_fwd (s2 LDS-DMA)") : rc;
     }
-    hipLaunchKernelGGL(conv_co1_kernel, dim3(a.tiles_x * a.tiles_y * a.n), dim3(256), lds, s, a);
-    return check_launch("conv2d_fwd (co1)");
-  }
-  if (n16_shape(d->in_c, d->ks, d->out_c) && d->cc == 32 * n16_ncb(d->in_c) && d->stride == 1 && d->up == 1 && d->pad == 1 &&
-      !ep->down2 && !ep->res_f32 && d->out_h == d->in_h && d->out_w == d->in_w &&
-      (long)d->n * d->in_h * d->in_w * d->in_cstride * 2 < (1L << 31)) {  // 32-bit buffer offsets
-    a.tiles_x = ceil_div(d->out_w, TW);
-    a.tiles_y = ceil_div(d->out_h, N16_TH);
-    // epilogue specialisations (see conv_n16_kernel): forward conv1-4 and the pull data gradients
-    const bool al = ((a.out_cs | a.out_co) & 3) == 0 && d->out_c == 16;
-    const int ep_mode = (al && a.act == 1 && a.bias && !a.res1 && !a.res2 && !a.aux && a.out_mode == 0) ? 1
-                        : (al && a.act == 3 && !a.bias && a.res1 && !(a.res_f32 & 1) && ((a.r1_cs | a.r1_co) & 3) == 0 &&
-                           !a.res2 && !a.aux && a.out_mode == 0)
-                            ? 2
-                            : 0;
-    switch ((d->cc / 32) * 4 + ep_mode) {
-      case 4: return launch_n16<1, 0>(a, s);
-      case 5: return launch_n16<1, 1>(a, s);
-      case 6: return launch_n16<1, 2>(a, s);
-      case 8: return launch_n16<2, 0>(a, s);
-      case 9: return launch_n16<2, 1>(a, s);
-      case 10: return launch_n16<2, 2>(a, s);
-      case 17: return launch_n16<4, 1>(a, s);
-      case 18: return launch_n16<4, 2>(a, s);
-      default: return launch_n16<4, 0>(a, s);
-    }
-  }
-  if (dgrad_s2_shape(d, ep, bias) && (long)d->n * d->out_h * d->out_w * ep->res1_cstride * 2 < (1L << 32) - 64)
-    return launch_dgrad_s2(d, a, s);
-  if (fwd_s2_shape(d, a)) return launch_fwd_s2(d, a, s);
-  if (pt_shape(d, ep) && (d->out_c == 16 || d->out_c == 32 || d->out_c == 64) &&
-      (d->in_c == 32 || d->in_c == 64 || d->in_c == 128))
-    return dispatch_pt(d, a, s);
-  {  // 64 -> 64 3x3: the weights resident in registers, wave-independent tiles (conv_wr.hip)
-    const int rc = conv_wr_launch(d, ep, x, wpk, g.kpk, bias, y, s, g_dry, g_dry_name, (int)sizeof(g_dry_name));
-    if (rc != -1) return rc;
-  }
-  {  // weights-resident persistent kernel for one-chunk convs with 17..64 outputs (large-pixel-count layers)
-    const int nt = fwd_nt(d->out_c);
-    const long npx = (long)d->n * d->out_h * d->out_w;
-    PwGeom pg;
-    if (ncob == 1 && (nt == 4 || nt == 2) && d->up != -2 && (npx >= 4096 || cc4) &&
-        (long)d->n * d->in_h * d->in_w * d->in_cstride * 2 < (1L << 31)) {  // 32-bit buffer offsets
-      // 8 waves x 2 rows (two waves per SIMD) when the LDS allows, else 4 waves x 2 rows
-      if (pw_geom(d, nt, 2, &pg, 8) && pg.nvx <= 512 * 7 && (d->out_h >= 16 || cc4)) {
-        // epilogue specialisations (store_tile_lds EP 3 / 4): activation forward / activation backward
-        const bool v8 = (a.out_c & 7) == 0 && ((a.out_cs | a.out_co) & 7) == 0 && !a.down2 && !a.res2 && !a.aux &&
-                        a.out_mode == 0 && a.res_f32 == 0;
-        const bool d2 = a.down2 && a.out_c == 64 && ((a.out_cs | a.out_co) & 3) == 0 && !a.bias && a.res1 && a.res_f32 == 0 &&
-                        ((a.r1_cs | a.r1_co) & 3) == 0 && (a.act == 3 || a.act == 4) && !a.res2 && !a.aux && a.out_mode == 0;
-        const int epm = (v8 && a.bias && !a.res1 && (a.act == 1 || a.act == 2)) ? 3
-                        : (v8 && !a.bias && a.res1 && ((a.r1_cs | a.r1_co) & 7) == 0 && (a.act == 3 || a.act == 4)) ? 4
-                        : d2 ? 5 : 0;
-        if (nt == 4 && epm == 0) {
-          switch (plain_ep(a)) {
-            case 6: return launch_pw<8, 2, 4, 7, 6>(a, pg, s);
-            case 7: return launch_pw<8, 2, 4, 7, 7>(a, pg, s);
-            case 8: return launch_pw<8, 2, 4, 7, 8>(a, pg, s);
-            default: break;
-          }
-        }
-        if (nt == 4) return epm == 3 ? launch_pw<8, 2, 4, 7, 3>(a, pg, s) : epm == 4 ? launch_pw<8, 2, 4, 7, 4>(a, pg, s)
-                            : epm == 5 ? launch_pw<8, 2, 4, 7, 5>(a, pg, s) : launch_pw<8, 2, 4, 7>(a, pg, s);
-        return epm == 3 ? launch_pw<8, 2, 2, 7, 3>(a, pg, s) : epm == 4 ? launch_pw<8, 2, 2, 7, 4>(a, pg, s)
-                                                                        : launch_pw<8, 2, 2, 7>(a, pg, s);
-      }
-      if (pw_geom(d, nt, 2, &pg, 4)) return nt == 4 ? launch_pw<4, 2, 4, 12>(a, pg, s) : launch_pw<4, 2, 2, 12>(a, pg, s);
-    }
-  }
-  if (cc4) {
-    set_error("conv2d_fwd: 4-channel chunks need the conv_pw path (stride 1, up 1/2, 64 outputs, 32-bit offsets)");
-    return CLIMSR_EINVAL;
-  }
-  if (g.lds_total > 160 * 1024) {
-    set_error("conv2d_fwd: LDS %zu exceeds 160 KiB (cc=%d)", g.lds_total, d->cc);
-    return CLIMSR_EINVAL;
-  }
-  if (mw == 4) {
-    // multi-chunk tiles whose per-thread staging fits 6 input + 9 weight vectors: chunk-pipelined variant
-    const int nrx = ceil_div(g.tph * g.tpw * (d->cc / 8), 256), nrw = ceil_div(g.nt * 16 * (g.kcpad / 8), 256);
-    if (g.nchunk > 1 && nrx <= 6 && nrw <= 9) {
-      // epilogue specialisations (store_tile_lds EP): residual forward (conv5, trunk_conv) / fp32 pull-x
-      const bool v8 = (a.out_c & 7) == 0 && ((a.out_cs | a.out_co) & 7) == 0 && ((a.r1_cs | a.r1_co) & 7) == 0 &&
-                      (!a.res2 || ((a.r2_cs | a.r2_co) & 7) == 0) && (!a.aux || ((a.aux_cs | a.aux_co) & 7) == 0) && !a.down2 &&
-                      a.act == 0 && a.res1;
-      if (v8 && a.bias && a.res_f32 == 0 && a.out_mode == 0 && !a.aux) return launch_fwd_ep<4, 4, 6, 9, 1>(a, ncob, g.lds_total, s);
-      if (v8 && !a.bias && (a.res_f32 & 1) && (!a.res2 || (a.res_f32 & 2)) && a.out_mode == 1)
-        return launch_fwd_ep<4, 4, 6, 9, 2>(a, ncob, g.lds_total, s);
-      // activation backward from a bf16 activation, bf16 out (the discriminator's layer-1 data gradient)
-      if (!a.bias && a.res1 && (a.act == 3 || a.act == 4) && a.res_f32 == 0 && !a.res2 && !a.aux && !a.down2 && a.out_mode == 0 &&
-          (a.out_c & 7) == 0 && ((a.out_cs | a.out_co | a.r1_cs | a.r1_co) & 7) == 0)
-        return launch_fwd_ep<4, 4, 6, 9, 4>(a, ncob, g.lds_total, s);
-      switch (plain_ep(a)) {
-        case 3: return launch_fwd_ep<4, 4, 6, 9, 3>(a, ncob, g.lds_total, s);
-        case 6: return launch_fwd_ep<4, 4, 6, 9, 6>(a, ncob, g.lds_total, s);
-        case 7: return launch_fwd_ep<4, 4, 6, 9, 7>(a, ncob, g.lds_total, s);
-        case 8: return a.bz ? launch_fwd_ep<4, 4, 6, 9, 10>(a, ncob, g.lds_total, s)
-                       : a.bn_part ? launch_fwd_ep<4, 4, 6, 9, 9>(a, ncob, g.lds_total, s) : launch_fwd_ep<4, 4, 6, 9, 8>(a, ncob, g.lds_total, s);
-        default: return launch_fwd<4, 4, 6, 9>(a, ncob, g.lds_total, s);
-      }
-    }
-    // large input tiles (stride 2: 33x33 pixels per 16x16 outputs) with several chunks: the deeper-prefetch
-    // variant (one workgroup per CU already, so the 18 staging vectors per thread cost no occupancy)
-    if (g.nchunk > 1 && nrx <= 18 && nrw <= 9) {
-      if (plain_ep(a) == 8) return launch_fwd_ep<4, 4, 18, 9, 8>(a, ncob, g.lds_total, s);
-      return launch_fwd<4, 4, 18, 9>(a, ncob, g.lds_total, s);
-    }
-    switch (plain_ep(a)) {
-      case 3: return launch_fwd_ep<4, 4, 0, 0, 3>(a, ncob, g.lds_total, s);
-      case 6: return launch_fwd_ep<4, 4, 0, 0, 6>(a, ncob, g.lds_total, s);
-      case 7: return launch_fwd_ep<4, 4, 0, 0, 7>(a, ncob, g.lds_total, s);
-      case 8: return launch_fwd_ep<4, 4, 0, 0, 8>(a, ncob, g.lds_total, s);
-      default: break;
-    }
-    return launch_fwd<4, 4>(a, ncob, g.lds_total, s);
-  }
-  switch (g.nt) {
-    case 1: return launch_fwd<2, 1>(a, ncob, g.lds_total, s);
-    case 2: return launch_fwd<2, 2>(a, ncob, g.lds_total, s);
-    default: return launch_fwd<2, 4>(a, ncob, g.lds_total, s);
+    case FAM_FWD:
+    case FAM_DMA: return fwd_generic_launch(r, a, s);
+    default: return launch_small(r, a, s);
   }
 }
 
 extern "C" const char* climsr_conv2d_fwd_kernel(const ClimsrConvDesc* d, const float* bias, const ClimsrEpilogue* ep) {
-  static uint16_t dummy[8];
-  g_dry = true;
-  g_dry_name[0] = 0;
-  const int rc = climsr_conv2d_fwd(d, dummy, dummy, bias, ep, dummy, nullptr);
-  g_dry = false;
-  return rc == CLIMSR_OK ? g_dry_name : "";
+  static thread_local char name[96];
+  name[0] = 0;
+  FwdRoute r;
+  if (fwd_route(d, bias != nullptr, ep, &r) == CLIMSR_OK) fwd_route_name(r, name, sizeof(name));
+  return name;
 }
 
-extern "C" int climsr_dgrad_single_output(int n, int h, int w, int ks, int pad, const uint16_t* dz, int dz_cstride, int dz_coff,
-                                          const float* weight, int c, int act, float slope, const uint16_t* res1, int res1_cstride,
-                                          int res1_coff, uint16_t* out, int out_cstride, int out_coff, void* stream);
+extern "C" int64_t climsr_conv2d_fwd_ch_parts(const ClimsrConvDesc* d, const ClimsrEpilogue* ep, int32_t* tiles_per_image) {
+  if (!d || !ep || d->cc <= 0) return 0;
+  ClimsrEpilogue e = *ep;
+  e.ch_part = (float*)1;  // (only its presence matters to the route)
+  FwdRoute r;
+  if (fwd_pick(d, false, &e, &r) != PICK_OK || r.family != FAM_WR || (r.ep != 3 && r.ep != 4)) return 0;
+  const int tpi = conv_wr_tiles_per_image(d);
+  if (tiles_per_image) *tiles_per_image = tpi;
+  return (int64_t)tpi * d->n;
+}
 
-extern "C" const char* climsr_dgrad_single_output_kernel(int ks, int c, int act) {
-  static uint16_t dummy[8];
-  static float wdummy[8];
-  g_dry = true;
-  g_dry_name[0] = 0;
-  const int rc = climsr_dgrad_single_output(1, 1, 1, ks, ks / 2, dummy, 8, 0, wdummy, c, act, 0.2f, dummy, 8, 0, dummy, c, 0, nullptr);
-  g_dry = false;
-  return rc == CLIMSR_OK ? g_dry_name : "";
+extern "C" int64_t climsr_conv2d_fwd_bn_parts(const ClimsrConvDesc* d, const ClimsrEpilogue* ep) {
+  if (!d || !ep || d->cc % 8 || d->cc <= 0 || d->stride < 1) return 0;
+  ClimsrEpilogue e = *ep;
+  e.bn_part = (double*)1;  // (only its presence matters to the route)
+  FwdRoute r;
+  if (fwd_pick(d, false, &e, &r) != PICK_OK || !r.parts) return 0;
+  if (d->up == -2) return (int64_t)ceil_div(d->in_w, 16) * ceil_div(d->in_h, 4 * (d->out_c == 64 ? 2 : 4)) * d->n;  // dz tiles
+  return (int64_t)ceil_div(d->out_w, TW) * ceil_div(d->out_h, 16) * d->n;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3522,7 +2656,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_co1m_kernel(WgArgs a) {
 
 template <int KS, int NCF>
 static int launch_wco1(const WgArgs& a, hipStream_t s) {
-  if (dry_run("conv_wgrad_co1m_kernel<%d, %d>", KS, NCF)) return CLIMSR_OK;
   auto k = conv_wgrad_co1m_kernel<KS, NCF>;  // (+16 B of static LDS: the dynamic cap leaves room for it)
   const size_t lds_x = (size_t)4 * WCO1_XT * (NCF * 16 + 8) * 2 + (size_t)4 * KS * 8 * WCO1_DZL * 2;
   const size_t lds_r = (size_t)4 * KS * NCF * 64 * 16;
@@ -3576,45 +2709,80 @@ static void wg_plan(const ClimsrConvDesc* d, WgPlan* w) {
   if (red > w->lds_total) w->lds_total = red;
 }
 
-static bool wg_ws(const ClimsrConvDesc* d, const WgPlan& w) {
-  return w.ci4 && d->ks == 9 && w.ncob == 1 && w.ntc == 4 && d->stride == 1;
+// The route of a weight gradient: the kernel kind with its template ids, the plan (co_rows / kw = the partial slabs'
+// layout for every kind; the tiling for the generic kinds) and the split count climsr_conv2d_wgrad_splits reports.
+enum WgKind { WG_PT, WG_CO1M, WG_W64_GLDS, WG_W64_TS, WG_W64_S2, WG_GENERIC, WG_WAVE_SPLIT };
+
+struct WgRoute {
+  int kind;
+  int ks, ncf;  // WG_CO1M <KS, NCF>; WG_PT <ncf>
+  WgPlan w;
+  int splits;
+};
+
+static WgRoute wg_route(const ClimsrConvDesc* d) {
+  WgRoute r{};
+  WgPlan& w = r.w;
+  wg_plan(d, &w);
+  if (wpt_shape(d)) {  // co_rows = out_c rounded to its 16/32/64 tile (wg_plan), kw = in_c
+    r.kind = WG_PT; r.ncf = d->out_c / 16 < 4 ? d->out_c / 16 : 4;
+    w.kw = d->in_c; r.splits = wpt_splits(d);
+  } else if (wco1_shape(d)) {
+    r.kind = WG_CO1M; r.ks = d->ks; r.ncf = d->in_c / 16;
+    w.co_rows = 16; r.splits = wco1_splits(d);
+  } else if (w64_shape(d)) {
+    // 8 waves (tap-split) pay off on the large-pixel-count convs (HRconv / upconv at 256^2: +8 %) and lose on the
+    // 64^2 dense-block GEMM (-19 %), measured with tools/perf_conv.py
+    const bool ts2 = d->stride == 1 && (long)d->n * d->out_h * d->out_w >= (1L << 20);
+    r.kind = d->stride == 2 ? WG_W64_S2 : ts2 ? WG_W64_TS : WG_W64_GLDS;
+    w.co_rows = d->out_c;
+    w.tiles_y = ceil_div(d->out_h, w64_th(d));
+    w.ntiles = d->n * w.tiles_x * w.tiles_y;
+    // one workgroup per CU: 256 / blocks splits
+    int blocks = (d->out_c / 64) * (d->in_c / 64);
+    int ns = ceil_div(256, blocks);
+    if (ns > w.ntiles) ns = w.ntiles;
+    r.splits = ns < 1 ? 1 : ns;
+  } else {
+    // <= 4 real input channels, 9x9, one 64-row block: all 21 tap groups per workgroup, 6 per wave
+    const bool ws = w.ci4 && d->ks == 9 && w.ncob == 1 && w.ntc == 4 && d->stride == 1;
+    r.kind = ws ? WG_WAVE_SPLIT : WG_GENERIC;
+    int ns = ceil_div(512, ws ? 1 : w.ntapb * w.ncib * w.ncob);
+    if (ns > w.ntiles) ns = w.ntiles;
+    r.splits = ns < 1 ? 1 : ns;
+  }
+  return r;
 }
 
-extern "C" int climsr_conv2d_wgrad_splits(const ClimsrConvDesc* d) {
-  if (wpt_shape(d)) return wpt_splits(d);
-  if (wco1_shape(d)) return wco1_splits(d);
-  if (w64_shape(d)) {  // one workgroup per CU: 256 / blocks splits
-    int blocks = (d->out_c / 64) * (d->in_c / 64);
-    int ntiles = d->n * ceil_div(d->out_w, TW) * ceil_div(d->out_h, w64_th(d));
-    int ns = ceil_div(256, blocks);
-    if (ns > ntiles) ns = ntiles;
-    return ns < 1 ? 1 : ns;
-  }
-  WgPlan w;
-  wg_plan(d, &w);
-  int base = wg_ws(d, w) ? 1 : w.ntapb * w.ncib * w.ncob;
-  int ns = ceil_div(512, base);
-  if (ns > w.ntiles) ns = w.ntiles;
-  if (ns < 1) ns = 1;
-  return ns;
-}
+extern "C" int climsr_conv2d_wgrad_splits(const ClimsrConvDesc* d) { return wg_route(d).splits; }
 
 extern "C" size_t climsr_conv2d_wgrad_workspace(const ClimsrConvDesc* d, int nsplit) {
-  if (wpt_shape(d)) {  // the reduce's layout: co_rows = out_c rounded to its 16/32/64 tile, kw = in_c
-    const int rows = round_up(d->out_c, 16), ntc = rows >= 64 ? 4 : (rows >= 32 ? 2 : 1);
-    const int co_rows = ceil_div(rows, ntc * 16) * ntc * 16;
-    return (size_t)nsplit * co_rows * d->in_c + (size_t)nsplit * co_rows;
-  }
-  if (wco1_shape(d)) return (size_t)nsplit * 16 * d->in_c * d->ks * d->ks + (size_t)nsplit * 16;
-  if (w64_shape(d)) return (size_t)nsplit * d->out_c * d->in_c * 9 + (size_t)nsplit * d->out_c;
-  WgPlan w;
-  wg_plan(d, &w);
+  const WgPlan w = wg_route(d).w;
   return (size_t)nsplit * w.co_rows * w.kw + (size_t)nsplit * w.co_rows;
+}
+
+// what climsr_conv2d_wgrad refuses of (d, dz_cstride) on route r
+static int wg_check(const ClimsrConvDesc* d, int dz_cstride, const WgRoute& r) {
+  if ((d->in_c % 8 && d->in_c != 4) || d->in_cstride % 8 || d->in_coff % 8 || dz_cstride % 8 || (d->up != 1 && d->up != 2) ||
+      (d->stride != 1 && d->stride != 2)) {
+    set_error("conv2d_wgrad: bad args");
+    return CLIMSR_EINVAL;
+  }
+  const bool w64 = r.kind == WG_W64_GLDS || r.kind == WG_W64_TS || r.kind == WG_W64_S2;
+  if (w64 && ((long)d->n * d->in_h * d->in_w * d->in_cstride * 2 >= (1L << 31) ||
+              (long)d->n * d->out_h * d->out_w * dz_cstride * 2 >= (1L << 31))) {  // 32-bit buffer offsets (BUF_OOB)
+    set_error("conv2d_wgrad: operands over 2 GiB (split the batch)");
+    return CLIMSR_EINVAL;
+  }
+  if ((r.kind == WG_GENERIC || r.kind == WG_WAVE_SPLIT) && r.w.lds_total > 160 * 1024) {
+    set_error("conv2d_wgrad: LDS %zu too large", r.w.lds_total);
+    return CLIMSR_EINVAL;
+  }
+  return CLIMSR_OK;
 }
 
 template <int NTC, int TB, int CI4>
 static int launch_wg(const WgArgs& a, int nblk, size_t lds, hipStream_t s) {
-  if (dry_run("conv_wgrad_kernel<%d, %d, %d, false>", NTC, TB, CI4)) return CLIMSR_OK;
   auto k = conv_wgrad_kernel<NTC, TB, CI4>;
   if (int e = lds_opt_in((const void*)k, 160 * 1024)) return e;
   hipLaunchKernelGGL(k, dim3(nblk, a.nsplit), dim3(256), lds, s, a);
@@ -3623,22 +2791,20 @@ static int launch_wg(const WgArgs& a, int nblk, size_t lds, hipStream_t s) {
 
 extern "C" int climsr_conv2d_wgrad(const ClimsrConvDesc* d, const uint16_t* x, const uint16_t* dz, int dz_cstride, float* partial,
                                    float* bias_partial, int nsplit, void* stream) {
-  if (!d || !x || !dz || !partial || nsplit <= 0 || (d->in_c % 8 && d->in_c != 4) || d->in_cstride % 8 || d->in_coff % 8 ||
-      dz_cstride % 8 ||
-      (d->up != 1 && d->up != 2) || (d->stride != 1 && d->stride != 2)) {
+  if (!d || !x || !dz || !partial || nsplit <= 0) {
     set_error("conv2d_wgrad: bad args");
     return CLIMSR_EINVAL;
   }
-  if (wpt_shape(d)) {
-    WgArgs a{};
-    a.x = x; a.dz = dz; a.part = partial; a.bpart = bias_partial;
-    a.n = d->n; a.in_c = d->in_c; a.in_cs = d->in_cstride; a.in_co = d->in_coff; a.out_h = d->out_h; a.out_w = d->out_w;
-    a.out_c = d->out_c; a.dz_cs = dz_cstride; a.nsplit = nsplit; a.kw = d->in_c;
-    const int rows = round_up(d->out_c, 16), ntc = rows >= 64 ? 4 : (rows >= 32 ? 2 : 1);
-    a.co_rows = ceil_div(rows, ntc * 16) * ntc * 16;
-    hipStream_t s = (hipStream_t)stream;
-    if (dry_run("conv_wgrad_pt_kernel<%d>", d->out_c / 16 < 4 ? d->out_c / 16 : 4)) return CLIMSR_OK;
-    switch (d->out_c / 16) {
+  const WgRoute r = wg_route(d);
+  const WgPlan& w = r.w;
+  if (int e = wg_check(d, dz_cstride, r)) return e;
+  hipStream_t s = (hipStream_t)stream;
+  WgArgs a{};
+  a.x = x; a.dz = dz; a.part = partial; a.bpart = bias_partial;
+  a.n = d->n; a.in_c = d->in_c; a.in_cs = d->in_cstride; a.in_co = d->in_coff; a.out_h = d->out_h; a.out_w = d->out_w;
+  a.out_c = d->out_c; a.dz_cs = dz_cstride; a.nsplit = nsplit; a.kw = w.kw; a.co_rows = w.co_rows;
+  if (r.kind == WG_PT) {
+    switch (r.ncf) {
       case 1: hipLaunchKernelGGL(conv_wgrad_pt_kernel<1>, dim3(nsplit), dim3(256), 0, s, a); break;
       case 2: hipLaunchKernelGGL(conv_wgrad_pt_kernel<2>, dim3(nsplit), dim3(256), 0, s, a); break;
       case 3: hipLaunchKernelGGL(conv_wgrad_pt_kernel<3>, dim3(nsplit), dim3(256), 0, s, a); break;
@@ -3646,85 +2812,41 @@ extern "C" int climsr_conv2d_wgrad(const ClimsrConvDesc* d, const uint16_t* x, c
     }
     return check_launch("conv2d_wgrad (1x1)");
   }
-  if (wco1_shape(d)) {
-    WgArgs a{};
-    a.x = x; a.dz = dz; a.part = partial; a.bpart = bias_partial;
-    a.n = d->n; a.in_h = d->in_h; a.in_w = d->in_w; a.in_c = d->in_c; a.in_cs = d->in_cstride; a.in_co = d->in_coff;
-    a.out_h = d->out_h; a.out_w = d->out_w; a.out_c = 1; a.dz_cs = dz_cstride; a.ks = d->ks; a.pad = d->pad;
-    a.nsplit = nsplit; a.kw = d->in_c * d->ks * d->ks; a.co_rows = 16;
+  a.in_h = d->in_h; a.in_w = d->in_w; a.ks = d->ks; a.pad = d->pad;
+  if (r.kind == WG_CO1M) {
+    a.out_c = 1;
     const long rows = (long)d->n * d->out_h * ceil_div(d->out_w, 64);
     a.tph = ceil_div(rows, (long)nsplit * 4);  // dz rows per wave segment (~one segment per wave)
     if (a.tph < 4) a.tph = 4;
     if (a.tph > d->out_h) a.tph = d->out_h;
-    hipStream_t s = (hipStream_t)stream;
-    switch (d->ks * 10 + d->in_c / 16) {
-      case 31: return launch_wco1<3, 1>(a, s);
-      case 32: return launch_wco1<3, 2>(a, s);
-      case 33: return launch_wco1<3, 3>(a, s);
-      case 34: return launch_wco1<3, 4>(a, s);
-      case 51: return launch_wco1<5, 1>(a, s);
-      case 52: return launch_wco1<5, 2>(a, s);
-      case 53: return launch_wco1<5, 3>(a, s);
-      default: return launch_wco1<5, 4>(a, s);
-    }
+#define WCO1_CASE(KS, NCF) \
+  if (r.ks == KS && r.ncf == NCF) return launch_wco1<KS, NCF>(a, s);
+    WCO1_CASE(3, 1) WCO1_CASE(3, 2) WCO1_CASE(3, 3) WCO1_CASE(3, 4) WCO1_CASE(5, 1) WCO1_CASE(5, 2) WCO1_CASE(5, 3)
+#undef WCO1_CASE
+    return launch_wco1<5, 4>(a, s);
   }
-  if (w64_shape(d)) {
-    if ((long)d->n * d->in_h * d->in_w * d->in_cstride * 2 >= (1L << 31) ||
-        (long)d->n * d->out_h * d->out_w * dz_cstride * 2 >= (1L << 31)) {  // 32-bit buffer offsets (BUF_OOB)
-      set_error("conv2d_wgrad: operands over 2 GiB (split the batch)");
-      return CLIMSR_EINVAL;
-    }
-    WgArgs a{};
-    a.x = x; a.dz = dz; a.part = partial; a.bpart = bias_partial;
-    a.n = d->n; a.in_h = d->in_h; a.in_w = d->in_w; a.in_c = d->in_c; a.in_cs = d->in_cstride; a.in_co = d->in_coff;
-    a.up = d->up; a.ks = 3; a.stride = 1; a.pad = 1; a.out_h = d->out_h; a.out_w = d->out_w;
-    a.out_c = d->out_c; a.dz_cs = dz_cstride;
-    a.tiles_x = ceil_div(d->out_w, TW); a.tiles_y = ceil_div(d->out_h, w64_th(d)); a.ntiles = d->n * a.tiles_x * a.tiles_y;
-    a.nsplit = nsplit; a.ncib = d->in_c / 64; a.co_rows = d->out_c; a.kw = d->in_c * 9;
+  a.up = d->up; a.stride = d->stride;
+  a.tiles_x = w.tiles_x; a.tiles_y = w.tiles_y; a.ntiles = w.ntiles;
+  if (r.kind == WG_W64_GLDS || r.kind == WG_W64_TS || r.kind == WG_W64_S2) {
+    a.ks = 3; a.pad = 1;
+    a.ncib = d->in_c / 64;
     a.dzp = W64_P; a.ntapb = 1; a.lds_x = 0;
-    a.stride = d->stride;
-    // 8 waves (tap-split) pay off on the large-pixel-count convs (HRconv / upconv at 256^2: +8 %) and lose on the
-    // 64^2 dense-block GEMM (-19 %), measured with tools/perf_conv.py
-    const bool ts2 = d->stride == 1 && (long)d->n * d->out_h * d->out_w >= (1L << 20);
     a.xcd = 1;
     const dim3 grid = dim3((d->out_c / 64) * (d->in_c / 64) * nsplit);
-    if (d->stride == 2) {
-      a.tph = W64<2>::TPH; a.tpw = W64<2>::TPW;
-      if (dry_run("conv_wgrad64_kernel<1, 2>")) return CLIMSR_OK;
-      if (int e = lds_opt_in((const void*)conv_wgrad64_kernel<1, 2>, 160 * 1024)) return e;
-      hipLaunchKernelGGL((conv_wgrad64_kernel<1, 2>), grid, dim3(256), std::max(2 * W64<2>::LDS, W64_EP_LDS), (hipStream_t)stream, a);
-    } else if (ts2) {
-      a.tph = W64<1>::TPH; a.tpw = W64<1>::TPW;
-      if (dry_run("conv_wgrad64_kernel<2, 1>")) return CLIMSR_OK;
-      if (int e = lds_opt_in((const void*)conv_wgrad64_kernel<2, 1>, 160 * 1024)) return e;
-      hipLaunchKernelGGL((conv_wgrad64_kernel<2, 1>), grid, dim3(512), std::max(W64<1>::LDS, W64_EP_LDS), (hipStream_t)stream, a);
-    } else {
-      a.tph = W64<1>::TPH; a.tpw = W64<1>::TPW;
-      if (dry_run("conv_wgrad64_glds_kernel")) return CLIMSR_OK;
-      if (int e = lds_opt_in((const void*)conv_wgrad64_glds_kernel, 160 * 1024)) return e;
-      hipLaunchKernelGGL(conv_wgrad64_glds_kernel, grid, dim3(256), std::max(W64G_LDS, W64_EP_LDS), (hipStream_t)stream, a);
-    }
+    const bool s2 = r.kind == WG_W64_S2, ts = r.kind == WG_W64_TS;
+    a.tph = s2 ? W64<2>::TPH : W64<1>::TPH; a.tpw = s2 ? W64<2>::TPW : W64<1>::TPW;
+    void (*k)(WgArgs) = s2 ? conv_wgrad64_kernel<1, 2> : ts ? conv_wgrad64_kernel<2, 1> : conv_wgrad64_glds_kernel;
+    const size_t lds = std::max(s2 ? 2 * W64<2>::LDS : ts ? W64<1>::LDS : W64G_LDS, W64_EP_LDS);
+    if (int e = lds_opt_in((const void*)k, 160 * 1024)) return e;
+    hipLaunchKernelGGL(k, grid, dim3(ts ? 512 : 256), lds, s, a);
     return check_launch("conv2d_wgrad (64x64 block)");
   }
-  WgPlan w;
-  wg_plan(d, &w);
-  if (w.lds_total > 160 * 1024) {
-    set_error("conv2d_wgrad: LDS %zu too large", w.lds_total);
-    return CLIMSR_EINVAL;
-  }
-  WgArgs a{};
-  a.x = x; a.dz = dz; a.part = partial; a.bpart = bias_partial;
-  a.n = d->n; a.in_h = d->in_h; a.in_w = d->in_w; a.in_c = d->in_c; a.in_cs = d->in_cstride; a.in_co = d->in_coff;
-  a.up = d->up; a.ks = d->ks; a.stride = d->stride; a.pad = d->pad; a.out_h = d->out_h; a.out_w = d->out_w;
-  a.out_c = d->out_c; a.dz_cs = dz_cstride;
-  a.tph = w.tph; a.tpw = w.tpw; a.dzp = w.dzp; a.tiles_x = w.tiles_x; a.tiles_y = w.tiles_y; a.ntiles = w.ntiles;
-  a.nsplit = nsplit; a.ntapb = w.ntapb; a.ncib = w.ncib; a.co_rows = w.co_rows; a.kw = w.kw;
+  a.tph = w.tph; a.tpw = w.tpw; a.dzp = w.dzp;
+  a.ntapb = w.ntapb; a.ncib = w.ncib;
   a.lds_x = (int)w.lds_x;
   int nblk = w.ntapb * w.ncib * w.ncob;
-  hipStream_t s = (hipStream_t)stream;
-  if (wg_ws(d, w)) {  // all 21 tap groups per workgroup, 6 per wave
+  if (r.kind == WG_WAVE_SPLIT) {
     a.ntapb = 1;
-    if (dry_run("conv_wgrad_kernel<4, 6, 1, true>")) return CLIMSR_OK;
     auto k = conv_wgrad_kernel<4, 6, 1, true>;
     if (int e = lds_opt_in((const void*)k, 160 * 1024)) return e;
     hipLaunchKernelGGL(k, dim3(1, nsplit), dim3(256), w.lds_total, s, a);
@@ -3743,13 +2865,21 @@ extern "C" int climsr_conv2d_wgrad(const ClimsrConvDesc* d, const uint16_t* x, c
 }
 
 extern "C" const char* climsr_conv2d_wgrad_kernel(const ClimsrConvDesc* d) {
-  static uint16_t dummy[8];
-  static float fdummy[8];
-  g_dry = true;
-  g_dry_name[0] = 0;
-  const int rc = climsr_conv2d_wgrad(d, dummy, dummy, 8, fdummy, fdummy, climsr_conv2d_wgrad_splits(d), nullptr);
-  g_dry = false;
-  return rc == CLIMSR_OK ? g_dry_name : "";
+  static thread_local char name[96];
+  name[0] = 0;
+  if (!d) {
+    set_error("conv2d_wgrad: bad args");
+    return name;
+  }
+  const WgRoute r = wg_route(d);
+  if (wg_check(d, 8, r) != CLIMSR_OK) return name;
+  const char* w64[] = {"conv_wgrad64_glds_kernel", "conv_wgrad64_kernel<2, 1>", "conv_wgrad64_kernel<1, 2>"};
+  if (r.kind == WG_PT) snprintf(name, sizeof(name), "conv_wgrad_pt_kernel<%d>", r.ncf);
+  else if (r.kind == WG_CO1M) snprintf(name, sizeof(name), "conv_wgrad_co1m_kernel<%d, %d>", r.ks, r.ncf);
+  else if (r.kind <= WG_W64_S2) snprintf(name, sizeof(name), "%s", w64[r.kind - WG_W64_GLDS]);
+  else if (r.kind == WG_WAVE_SPLIT) snprintf(name, sizeof(name), "conv_wgrad_kernel<4, 6, 1, true>");
+  else snprintf(name, sizeof(name), "conv_wgrad_kernel<%d, %d, %d, false>", r.w.ntc, r.w.tb, r.w.ci4);
+  return name;
 }
 
 // 256 threads = 32 consecutive outputs x 8 split groups (8 independent load chains per output,

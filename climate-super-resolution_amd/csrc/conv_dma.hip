@@ -1,4 +1,4 @@
-// LDS-DMA implicit-GEMM conv for CDNA4 (gfx950): the 3x3 / stride-1 / 32-channel-chunk shapes of conv.hip's GEO 1
+// LDS-DMA implicit-GEMM conv for CDNA4 (gfx950): the 3x3 / stride-1 / 32-channel-chunk shapes of conv_fwd.hip's GEO 1
 // path (VGG19 perceptual-loss convs climsr/losses/perceptual.py:22-36, RDB conv5 / its data gradient
 // climsr/models/esrgan.py:26,32-38, the discriminator's stride-1 layers climsr/models/rfb_esrgan.py:28-52).
 #include <algorithm>

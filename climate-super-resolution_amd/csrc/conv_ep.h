@@ -1,5 +1,6 @@
-// Shared by the conv translation units (conv.hip, conv_dma.hip): the forward / data-gradient kernel arguments and
-// the coalesced store epilogue (store_tile_lds) with its BatchNorm-partial helpers.
+// Shared by the conv kernel units (conv.hip, conv_fwd.hip, conv_pw.hip, conv_dma.hip): the forward / data-gradient kernel
+// arguments, the coalesced store epilogue (store_tile_lds) with its BatchNorm-partial helpers and the persistent tile
+// walk.  The route and the host-side launcher declarations are in conv_route.h.
 #pragma once
 #include "common.h"
 
@@ -47,6 +48,26 @@ __device__ __forceinline__ int xcd_major(int b, int n) {
   const int x = b & 7, j = b >> 3, q = n >> 3, r = n & 7;
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
 }
+
+// Persistent tile walk, XCD-aware.  Workgroups are dispatched round-robin over the 8 XCDs and each XCD
+// has its own L2, so block b walks a contiguous span of tiles owned by XCD b % 8: tiles that run at the
+// same time on one XCD are spatial neighbours and share their input halo rows in that L2.
+struct TileWalk {
+  int first, step, end;
+  __device__ explicit TileWalk(int ntiles) {
+    const int grid = (int)gridDim.x, b = (int)blockIdx.x;
+    if (grid % 8 == 0 && grid >= 64) {
+      const int span = (ntiles + 7) / 8, xcd = b % 8;
+      first = xcd * span + b / 8;
+      step = grid / 8;
+      end = min(ntiles, (xcd + 1) * span);
+    } else {
+      first = b;
+      step = grid;
+      end = ntiles;
+    }
+  }
+};
 
 // Epilogue residual operands: 4 consecutive channels, bf16 (8 B) or fp32 (16 B), kept raw until use so
 // that all loads of a round are in flight together.

@@ -19,7 +19,7 @@
 #include <algorithm>
 #include <stdio.h>
 
-#include "conv_ep.h"
+#include "conv_route.h"
 #include "mfma_agpr.h"
 
 namespace {
@@ -283,7 +283,7 @@ namespace climsr {
 // the conv_wr epilogue for (d, ep), or -1 when the conv is not this kernel's: 0 bias / activation, bf16 out; 1 + bf16
 // residual; 2 activation backward from the stored activation (no bias); 3 bias / activation, fp32 out (+ per-tile
 // channel sums); 4 bias / activation, bf16 out + per-tile channel sums (of the fp32 values).
-int conv_wr_ep(const ClimsrConvDesc* d, const ClimsrEpilogue* ep, const float* bias) {
+int conv_wr_ep(const ClimsrConvDesc* d, const ClimsrEpilogue* ep, bool bias) {
   const bool res = ep->res1 != nullptr;
   int epk = -1;
   if (ep->out_mode == 0 && !res && ep->act >= 0 && ep->act <= 2) epk = ep->ch_part ? 4 : 0;
@@ -302,27 +302,14 @@ int conv_wr_ep(const ClimsrConvDesc* d, const ClimsrEpilogue* ep, const float* b
   return epk;
 }
 
-// tiles (rows of ch_part) of the conv, and per image; 0 when conv_wr does not take (d, ep)
-long conv_wr_ch_parts(const ClimsrConvDesc* d, const ClimsrEpilogue* ep, int* tiles_per_image) {
-  ClimsrEpilogue e = *ep;
-  e.ch_part = (float*)1;  // (only its presence matters here)
-  const int k = conv_wr_ep(d, &e, nullptr);
-  if (k != 3 && k != 4) return 0;
-  const int tpi = ceil_div(d->out_w, WR_TC) * ceil_div(d->out_h, WR_TR);
-  if (tiles_per_image) *tiles_per_image = tpi;
-  return (long)tpi * d->n;
-}
+// tiles (rows of ch_part) of one image
+int conv_wr_tiles_per_image(const ClimsrConvDesc* d) { return ceil_div(d->out_w, WR_TC) * ceil_div(d->out_h, WR_TR); }
 
-int conv_wr_launch(const ClimsrConvDesc* d, const ClimsrEpilogue* ep, const uint16_t* x, const uint16_t* wpk, int kpk,
-                   const float* bias, void* y, hipStream_t s, bool dry, char* name, int name_len) {
-  const int epk = conv_wr_ep(d, ep, bias);
+// epk = conv_wr_ep(d, ep, bias) >= 0, as the route recorded it
+int conv_wr_launch(int epk, const ClimsrConvDesc* d, const ClimsrEpilogue* ep, const uint16_t* x, const uint16_t* wpk, int kpk,
+                   const float* bias, void* y, hipStream_t s) {
   const bool res = ep->res1 != nullptr;
   const long opx = (long)d->n * d->out_h * d->out_w;
-  if (epk < 0 || kpk < 576) return -1;
-  if (dry) {
-    snprintf(name, name_len, "conv_wr_kernel<%d>", epk);
-    return CLIMSR_OK;
-  }
   WrArgs a;
   a.x = x; a.w = wpk; a.bias = bias; a.y = (uint16_t*)y; a.res1 = (const uint16_t*)ep->res1; a.ch_part = ep->ch_part;
   a.n = d->n; a.in_h = d->in_h; a.in_w = d->in_w; a.in_cs = d->in_cstride; a.in_co = d->in_coff; a.up = d->up;

@@ -179,7 +179,7 @@ int64_t climsr_conv2d_fwd_bn_parts(const ClimsrConvDesc* d, const ClimsrEpilogue
 /* Name of the kernel climsr_conv2d_fwd launches for these arguments (as rocprof reports it; "" if invalid).
  * Launches nothing; used to label per-kernel timings and PMC traffic. */
 const char* climsr_conv2d_fwd_kernel(const ClimsrConvDesc* d, const float* bias, const ClimsrEpilogue* ep);
-/* Dry-run kernel-name queries (profiler labels straight from the dispatch; nothing is launched): the weight-gradient
+/* Kernel-name queries (profiler labels straight from the dispatch's route; nothing is launched): the weight-gradient
  * kernel climsr_conv2d_wgrad would launch for d (with climsr_conv2d_wgrad_splits(d) splits), and the data-gradient
  * stencil climsr_dgrad_single_output would launch for (ks, c, act).  "" if the arguments are unsupported. */
 const char* climsr_conv2d_wgrad_kernel(const ClimsrConvDesc* d);

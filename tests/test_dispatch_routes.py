@@ -1,7 +1,8 @@
 """Which kernel every hot conv of the product takes, pinned on the CPU.
 
-The dispatcher's dry-run entry points (climsr_conv2d_fwd_kernel / climsr_conv2d_wgrad_kernel: the same C++ dispatch
-code, which records the kernel it would launch instead of launching) are asked through the product's own call sites:
+The dispatcher's name entry points (climsr_conv2d_fwd_kernel / climsr_conv2d_wgrad_kernel: they format the route that
+climsr_conv2d_fwd / climsr_conv2d_wgrad decide and launch from, fwd_route() / wg_route()) are asked through the
+product's own call sites:
 ConvPlan.fwd / wgrad and GroupedWgrad.run with the arguments models/esrgan.py, losses/perceptual.py and
 models/rfb_esrgan.py pass at the GAN-step shapes (config 3: B=32, 64^2 -> 256^2; VGG on 64 images).  The launch
 observer (ops.PROFILER) records the names and runs nothing, so no GPU is needed and the tensors are placeholders.
@@ -120,7 +121,7 @@ def test_stride2_dma_route_refuses_inputs_past_2gib(routes):
     assert p.bn_parts(64, hw, hw, 8, 64) == 8 * (hw // 32) ** 2
     p.fwd(bf(), 64, 0, hw, hw, bf(), 64, 0, 8, use_bias=False)
     assert last(routes) == "conv_fwd_s2_dma_kernel<false>"
-    # with partials requested the refused shape is the dispatcher's existing error (the dry run names no kernel),
+    # with partials requested the refused shape is the dispatcher's existing error (the query names no kernel),
     # while the production shapes keep conv_fwd_s2_dma_kernel<true> (test_discriminator_bn_conv_routes)
     p.fwd(bf(), 64, 0, hw, hw, bf(), 64, 0, 32, use_bias=False, bn_part=torch.empty(1, dtype=torch.float64))
     assert last(routes) == ""

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Diagnostic variants of libclimsr_hip.so (CPU-side build; they travel to the GPU box in-tree) under
-# climate-super-resolution_amd/csrc/diag/<name>/libclimsr_hip.so: conv DIAG modes (conv.hip CLIMSR_DIAG_MODE) and
+# climate-super-resolution_amd/csrc/diag/<name>/libclimsr_hip.so: conv DIAG modes (conv_fwd.hip CLIMSR_DIAG_MODE) and
 # LDS-DMA conv A/B switches (conv_dma.hip CLIMSR_DMA_*).  Timing experiments only: their results are not valid.
 #   bash tools/diag_build.sh conv2:-DCLIMSR_DIAG_MODE=2 dmadirect:-DCLIMSR_DMA_DIRECT=1 ...
 set -e
