@@ -231,22 +231,10 @@ class AdamW(torch.optim.Optimizer):
                     if "m" not in ps:
                         ps["m"] = torch.zeros_like(p)
                         ps["v"] = torch.zeros_like(p)
-                    g = p.grad.contiguous()
-                    if grad_scale is not None:
-                        g = g.clone() if g.data_ptr() == p.grad.data_ptr() else g  # .grad stays unclipped
-                        _launch("grad_scale", lambda: lib.climsr_scale_f32(ptr(g), g.numel(), ptr(grad_scale), _lib.stream_ptr()),
-                                nbytes=8 * g.numel())
-                    if self._COUPLED:
-                        _launch("adam", lambda: lib.climsr_adam_step(p.numel(), ptr(p), ptr(g), ptr(ps["m"]), ptr(ps["v"]), ptr(hp),
-                                                                     0, 0, None, _lib.stream_ptr()), nbytes=28 * p.numel())
-                        continue
-                    _launch("adamw", lambda: lib.climsr_adamw_step(p.numel(), ptr(p), ptr(g), ptr(ps["m"]), ptr(ps["v"]), ptr(hp),
-                                                                   _lib.stream_ptr()), nbytes=28 * p.numel())
+                    # with grad_scale the scaled entry only reads the gradient: .grad stays unclipped
+                    _adamw_flat(lib, None, p, p.grad.contiguous(), ps["m"], ps["v"], hp, _lib.stream_ptr(), grad_scale, self._COUPLED)
         if self.owner is not None:
-            if mirrored and _mirror_of(self.owner) is not None:
-                self.owner.repack_weights(mirror_done=True)
-            else:
-                self.owner.repack_weights()
+            _repack_after(self.owner, mirrored)
         return loss
 
 
@@ -256,77 +244,98 @@ def _mirror_of(module):
     return fn() if fn is not None else None
 
 
-def _adamw_flat(lib, module, flat, gflat, m, v, hp, stream, grad_scale=None, coupled=False):
-    """One fused AdamW launch over a flat buffer; when ``module`` mirrors part of it in bf16 (``bf16_mirror()``), the
-    same pass writes that copy.  ``grad_scale`` (device scalar): the update reads gradient * grad_scale.  ``coupled``:
-    the Adam update (L2 term in the gradient) instead."""
-    mir = _mirror_of(module) if module is not None else None
-    if coupled:
-        lo, n, buf = mir if mir is not None else (0, 0, None)
-        if grad_scale is not None:
-            _launch("adam_scaled", lambda: lib.climsr_adam_step_scaled(flat.numel(), ptr(flat), ptr(gflat), ptr(m), ptr(v), ptr(hp),
-                                                                       ptr(grad_scale), lo, n, ptr(buf), stream),
-                    nbytes=28 * flat.numel() + 2 * n)
-        else:
-            _launch("adam", lambda: lib.climsr_adam_step(flat.numel(), ptr(flat), ptr(gflat), ptr(m), ptr(v), ptr(hp), lo, n,
-                                                         ptr(buf), stream), nbytes=28 * flat.numel() + 2 * n)
-        return
-    if grad_scale is not None:
-        lo, n, buf = mir if mir is not None else (0, 0, None)
-        _launch("adamw_scaled", lambda: lib.climsr_adamw_step_scaled(flat.numel(), ptr(flat), ptr(gflat), ptr(m), ptr(v), ptr(hp),
-                                                                     ptr(grad_scale), lo, n, ptr(buf), stream),
-                nbytes=28 * flat.numel() + 2 * n)
-    elif mir is None:
-        _launch("adamw", lambda: lib.climsr_adamw_step(flat.numel(), ptr(flat), ptr(gflat), ptr(m), ptr(v), ptr(hp), stream),
-                nbytes=28 * flat.numel())
+def _repack_after(module, mirrored: bool = True) -> None:
+    """Re-pack ``module``'s bf16 weight layouts after an update; ``mirrored``: ``_adamw_flat`` wrote its bf16 mirror."""
+    if mirrored and _mirror_of(module) is not None:
+        module.repack_weights(mirror_done=True)
     else:
-        lo, n, buf = mir
-        _launch("adamw", lambda: lib.climsr_adamw_step_mirror(flat.numel(), ptr(flat), ptr(gflat), ptr(m), ptr(v), ptr(hp), lo, n,
-                                                              ptr(buf), stream), nbytes=28 * flat.numel() + 2 * n)
+        module.repack_weights()
 
 
-class GraphedAdamW:
-    """AdamW + OneCycleLR with all scalars on the device, for hipGraph-captured training steps.
+def _adamw_flat(lib, module, p, g, m, v, hp, stream, grad_scale=None, coupled=False):
+    """One fused update launch over ``p`` (a network's flat buffer, or one parameter with ``module`` None); when
+    ``module`` mirrors part of the buffer in bf16 (``bf16_mirror()``), the same pass writes that copy.  ``grad_scale``
+    (device scalar): the update reads gradient * grad_scale and leaves the gradient as it is.  ``coupled``: the Adam
+    update (L2 term in the gradient) instead of AdamW's.  The only caller of the library's ``climsr_*_step*`` entries."""
+    mir = _mirror_of(module) if module is not None else None
+    lo, mn, buf = mir if mir is not None else (0, 0, None)
+    n = p.numel()
+    args = (n, ptr(p), ptr(g), ptr(m), ptr(v), ptr(hp))
+    window = (lo, mn, ptr(buf), stream)
+    if grad_scale is not None:
+        label, fn = ("adam_scaled", lib.climsr_adam_step_scaled) if coupled else ("adamw_scaled", lib.climsr_adamw_step_scaled)
+        args += (ptr(grad_scale),) + window
+    elif coupled:
+        label, fn, args = "adam", lib.climsr_adam_step, args + window
+    elif mir is not None:
+        label, fn, args = "adamw", lib.climsr_adamw_step_mirror, args + window
+    else:
+        label, fn, args = "adamw", lib.climsr_adamw_step, args + (stream,)
+    _launch(label, lambda: fn(*args), nbytes=28 * n + 2 * mn)
 
-    ``step()`` launches: schedule kernel (lr, beta1, bias corrections from a device step counter),
-    the fused update over the flat buffer, and the bf16 weight repack.  With ``max_grad_norm`` it first takes the L2
-    norm of the flat gradient (``GradNorm``) and the update reads the gradient times the device-side clip coefficient.  Semantics equal
-    torch AdamW stepped before OneCycleLR.step() each iteration (Lightning interval="step").
-    """
 
-    def __init__(self, module, lr: float = 1e-4, total_steps: int = 1000, weight_decay: float = 1e-4, pct_start: float = 0.05,
-                 div_factor: float = 2.0, final_div_factor: float = 100.0, betas=(0.9, 0.999), eps: float = 1e-8,
-                 max_grad_norm: Optional[float] = None):
-        self.module = module
-        if max_grad_norm is not None and not max_grad_norm > 0:
+class _DeviceStep:
+    """An optimizer step with every scalar on the device, so that a captured hipGraph replays it: what ``GraphedAdamW``
+    and ``DeviceStepped`` share.  ``step()`` launches the schedule kernel (``_launch_schedule``: lr, betas and bias
+    corrections from the device counters ``state``, which it advances, into the ``hp`` row), with ``max_grad_norm`` the
+    L2 norm of the flat gradient (``_grads``) giving the device clip coefficient, the fused update reading it, and the
+    bf16 re-pack.  It returns that coefficient (or None), allocates nothing and reads nothing back."""
+
+    def __init__(self, module, m, v, state, coupled: bool, max_grad_norm: Optional[float], grad_norm: Optional[GradNorm]):
+        self.module, self.m, self.v, self.state, self.coupled = module, m, v, state, coupled
+        self.hp = torch.zeros(8, dtype=torch.float32, device=module._flat.device)
+        self.max_grad_norm, self.grad_norm = max_grad_norm, grad_norm
+
+    @staticmethod
+    def _clip_norm(module, max_grad_norm, gn_of) -> Optional[GradNorm]:
+        """The ``GradNorm`` (``gn_of(module)``) a step clipping at ``max_grad_norm`` needs; None without clipping."""
+        if max_grad_norm is None:
+            return None
+        if not max_grad_norm > 0:
             raise ValueError(f"max_grad_norm must be positive, got {max_grad_norm!r}")
-        self.max_grad_norm = max_grad_norm
-        self.grad_norm = GradNorm(module) if max_grad_norm is not None else None
-        if self.grad_norm is not None:
-            self.grad_norm._prepare(_lib.load())  # offsets table and workspace now: step() may run inside a capture
-        flat = module._flat
-        self.m = torch.zeros_like(flat)
-        self.v = torch.zeros_like(flat)
-        self.state = torch.zeros(2, dtype=torch.float64, device=flat.device)
-        self.hp = torch.zeros(8, dtype=torch.float32, device=flat.device)
-        self.cfg = (int(total_steps), float(lr), float(pct_start), float(div_factor), float(final_div_factor), float(betas[1]),
-                    float(eps), float(weight_decay))
+        gn = gn_of(module)
+        if module._flat.is_cuda:
+            gn._prepare(_lib.load())  # offsets table and workspace now: step() may run inside a capture
+        return gn
+
+    # subclasses: _launch_schedule(lib, stream) launches the schedule kernel on self.state / self.hp; _grads() returns
+    # (the flat gradient tensor, whether it is module._flat_grad already holding the gradients)
 
     def step(self):
         lib = _lib.load()
         s = _lib.stream_ptr()
-        ts, lr, pct, div, fdiv, b2, eps, wd = self.cfg
-        _launch("adamw_hparams", lambda: lib.climsr_adamw_hparams(ptr(self.state), ts, lr, pct, div, fdiv, b2, eps, wd, ptr(self.hp),
-                                                                  s))
-        flat = self.module._flat
+        self._launch_schedule(lib, s)
+        gflat, gathered = self._grads()
         coef = None
         if self.grad_norm is not None:  # L2 norm of the flat gradient -> clip coefficient, kept on the device
-            coef = self.grad_norm(2, self.max_grad_norm, gathered=True)[2]
-        _adamw_flat(lib, self.module, flat, self.module._flat_grad, self.m, self.v, self.hp, s, coef)
-        if _mirror_of(self.module) is not None:
-            self.module.engine().repack(mirror_done=True)
-        else:
-            self.module.engine().repack()
+            coef = self.grad_norm(2, self.max_grad_norm, gathered=gathered)[2]
+        _adamw_flat(lib, self.module, self.module._flat, gflat, self.m, self.v, self.hp, s, coef, self.coupled)
+        _repack_after(self.module)
+        return coef
+
+
+class GraphedAdamW(_DeviceStep):
+    """AdamW + OneCycleLR with all scalars on the device, for hipGraph-captured training steps (``bench.py``'s step).
+
+    ``step()`` is ``_DeviceStep``'s with ``climsr_adamw_hparams`` as the schedule kernel and ``module._flat_grad`` taken
+    as it stands (no per-step host work).  Semantics: torch AdamW stepped before OneCycleLR.step() each iteration."""
+
+    def __init__(self, module, lr: float = 1e-4, total_steps: int = 1000, weight_decay: float = 1e-4, pct_start: float = 0.05,
+                 div_factor: float = 2.0, final_div_factor: float = 100.0, betas=(0.9, 0.999), eps: float = 1e-8,
+                 max_grad_norm: Optional[float] = None):
+        flat = module._flat
+        super().__init__(module, torch.zeros_like(flat), torch.zeros_like(flat), torch.zeros(2, dtype=torch.float64, device=flat.device),
+                         False, max_grad_norm, self._clip_norm(module, max_grad_norm, GradNorm))
+        self.cfg = (int(total_steps), float(lr), float(pct_start), float(div_factor), float(final_div_factor), float(betas[1]),
+                    float(eps), float(weight_decay))
+
+    def _launch_schedule(self, lib, stream) -> None:
+        ts, lr, pct, div, fdiv, b2, eps, wd = self.cfg
+        _launch("adamw_hparams", lambda: lib.climsr_adamw_hparams(ptr(self.state), ts, lr, pct, div, fdiv, b2, eps, wd, ptr(self.hp),
+                                                                  stream))
+
+    def _grads(self):
+        return self.module._flat_grad, True
 
 
 class Adam(AdamW):
@@ -465,13 +474,12 @@ def _describe_schedule(optimizer, scheduler):
                               "implemented (the polynomial schedule stays on the eager path)")
 
 
-class DeviceStepped:
+class DeviceStepped(_DeviceStep):
     """The device-stepped form of an eager ``(optimizer, scheduler or None)`` pair, for captured training steps:
-    ``GraphedAdamW`` generalised to ``core.optim.AdamW`` / ``Adam`` and every schedule ``climsr_opt_hparams`` knows.
+    ``core.optim.AdamW`` / ``Adam`` under every schedule ``climsr_opt_hparams`` knows.
 
-    ``step()`` launches the schedule kernel (lr, betas and bias corrections from the device counters, which it
-    increments), with ``max_grad_norm`` the L2 norm of the flat gradient, the fused update (reading the device clip
-    coefficient) and the bf16 re-pack; it returns that coefficient (or None).  m and v are the eager optimizer's own
+    ``step()`` is ``_DeviceStep``'s with ``climsr_opt_hparams`` as the schedule kernel and the gradients gathered into
+    the network's flat gradient buffer when autograd delivered them apart.  m and v are the eager optimizer's own
     tensors, the counters start from its ``state["group0"]["step"]`` and the scheduler's ``last_epoch``, and ``flush()``
     writes them back to the host objects with one host read, after which those are what the eager pair would be.
     A pair it cannot express raises ``NotImplementedError`` naming the pair."""
@@ -487,54 +495,38 @@ class DeviceStepped:
             raise NotImplementedError(f"the pair {pair} cannot be stepped on the device: the optimizer must hold the "
                                       "parameters of one native flat-parameter network in one group")
         self.kind, self.sched_cfg = _describe_schedule(optimizer, scheduler)
-        if max_grad_norm is not None and not max_grad_norm > 0:
-            raise ValueError(f"max_grad_norm must be positive, got {max_grad_norm!r}")
-        self.optimizer, self.scheduler, self.module, self.max_grad_norm = optimizer, scheduler, module, max_grad_norm
-        self.coupled = optimizer._COUPLED
+        grad_norm = self._clip_norm(module, max_grad_norm, GradNorm.of)
+        self.optimizer, self.scheduler = optimizer, scheduler
         flat = module._flat
         st = optimizer.state.setdefault("group0", {})
         if "m" not in st:
             st["m"], st["v"] = torch.zeros_like(flat), torch.zeros_like(flat)
-        self.m, self.v = st["m"], st["v"]
         last_epoch = scheduler.last_epoch if scheduler is not None else 0
-        self.state = torch.tensor([float(st.get("step", 0)), float(last_epoch)], dtype=torch.float64).to(flat.device)
-        self.hp = torch.zeros(8, dtype=torch.float32, device=flat.device)
-        self.grad_norm = None
-        if max_grad_norm is not None:
-            self.grad_norm = GradNorm.of(module)
-            if flat.is_cuda:
-                self.grad_norm._prepare(_lib.load())  # offsets table and workspace now: step() may run inside a capture
+        state = torch.tensor([float(st.get("step", 0)), float(last_epoch)], dtype=torch.float64).to(flat.device)
+        super().__init__(module, st["m"], st["v"], state, optimizer._COUPLED, max_grad_norm, grad_norm)
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         self.optimizer.zero_grad(set_to_none=set_to_none)
 
-    def step(self):
-        lib = _lib.load()
-        s = _lib.stream_ptr()
+    def _launch_schedule(self, lib, stream) -> None:
         group, c = self.optimizer.param_groups[0], self.sched_cfg
         b1, b2 = group["betas"]
         lr = c.get("lr", group["lr"])  # a scheduler's base / max lr; without one the group's current lr
         _launch("opt_hparams", lambda: lib.climsr_opt_hparams(
             ptr(self.state), self.kind, float(lr), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
             c.get("warmup", 0.0), c.get("total", 0.0), c.get("cycles", 0.0), c.get("pct_start", 0.0), c.get("div_factor", 0.0),
-            c.get("final_div_factor", 0.0), ptr(self.hp), s))
+            c.get("final_div_factor", 0.0), ptr(self.hp), stream))
+
+    def _grads(self):
         module = self.module
         flat = module._flat
         if flat.numel() != self.m.numel() or flat.device != self.m.device:
             raise RuntimeError("DeviceStepped: the network's flat parameter buffer changed size or device; build the "
                                "optimizers again")
-        gflat = _gather_flat_grad(module, flat, group["params"])
+        gflat = _gather_flat_grad(module, flat, self.optimizer.param_groups[0]["params"])
         if gflat is None:
             raise RuntimeError("DeviceStepped.step: a parameter has no gradient in the network's flat gradient buffer")
-        coef = None
-        if self.grad_norm is not None:
-            coef = self.grad_norm(2, self.max_grad_norm, gathered=gflat.data_ptr() == module._flat_grad.data_ptr())[2]
-        _adamw_flat(lib, module, flat, gflat, self.m, self.v, self.hp, s, coef, self.coupled)
-        if _mirror_of(module) is not None:
-            module.engine().repack(mirror_done=True)
-        else:
-            module.engine().repack()
-        return coef
+        return gflat, gflat.data_ptr() == module._flat_grad.data_ptr()
 
     def flush(self) -> None:
         """The device counters into the host objects (one host read): the optimizer's step count, the scheduler's

@@ -349,11 +349,29 @@ extern "C" int climsr_mse_loss_grad(const float* a, const float* b, int64_t n, c
 // ------------------------------------------------------------------------------------------
 __device__ double cos_anneal(double start, double end, double pct) { return end + (start - end) / 2.0 * (cos(M_PI * pct) + 1.0); }
 
+// The 8-float hp row the update kernels read, for optimizer step `step` (the one about to be taken: torch increments
+// before use) under the scheduler's last_epoch `sched`; both counters advance.
+__device__ void write_hp_row(double lr, double b1, double beta2, double eps, double wd, double step, double sched, float* hp,
+                             double* state) {
+  double bc1 = 1.0 - pow(b1, step);
+  double bc2 = 1.0 - pow(beta2, step);
+  hp[0] = (float)lr;
+  hp[1] = (float)b1;
+  hp[2] = (float)beta2;
+  hp[3] = (float)eps;
+  hp[4] = (float)wd;
+  hp[5] = (float)(lr / bc1);
+  hp[6] = (float)sqrt(bc2);
+  hp[7] = 0.f;
+  state[0] = step;
+  state[1] = sched + 1.0;
+}
+
 __global__ void adamw_hparams_kernel(double* state, int total_steps, double max_lr, double pct_start, double div_factor,
                                      double final_div_factor, double beta2, double eps, double wd, float* hp) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  double step = state[0] + 1.0;  // optimizer step about to be taken (torch increments before use)
-  double sched = state[1];       // scheduler last_epoch
+  double step = state[0] + 1.0;
+  double sched = state[1];
   double initial_lr = max_lr / div_factor;
   double min_lr = initial_lr / final_div_factor;
   double end0 = pct_start * total_steps - 1.0, end1 = (double)total_steps - 1.0;
@@ -367,18 +385,7 @@ __global__ void adamw_hparams_kernel(double* state, int total_steps, double max_
     lr = cos_anneal(max_lr, min_lr, pct);
     b1 = cos_anneal(0.85, 0.95, pct);
   }
-  double bc1 = 1.0 - pow(b1, step);
-  double bc2 = 1.0 - pow(beta2, step);
-  hp[0] = (float)lr;
-  hp[1] = (float)b1;
-  hp[2] = (float)beta2;
-  hp[3] = (float)eps;
-  hp[4] = (float)wd;
-  hp[5] = (float)(lr / bc1);
-  hp[6] = (float)sqrt(bc2);
-  hp[7] = 0.f;
-  state[0] = step;
-  state[1] = sched + 1.0;
+  write_hp_row(lr, b1, beta2, eps, wd, step, sched, hp, state);
 }
 
 extern "C" int climsr_adamw_hparams(double* state, int total_steps, double max_lr, double pct_start, double div_factor,
@@ -413,19 +420,7 @@ __global__ void opt_hparams_kernel(double* state, int kind, double base_lr, doub
     const double progress = (s - warmup) / fmax(1.0, total - warmup);
     lam = progress >= 1.0 ? 0.0 : fmax(0.0, 0.5 * (1.0 + cos(M_PI * fmod(cycles * progress, 1.0))));
   }
-  const double lr = base_lr * lam;
-  const double bc1 = 1.0 - pow(beta1, step);
-  const double bc2 = 1.0 - pow(beta2, step);
-  hp[0] = (float)lr;
-  hp[1] = (float)beta1;
-  hp[2] = (float)beta2;
-  hp[3] = (float)eps;
-  hp[4] = (float)wd;
-  hp[5] = (float)(lr / bc1);
-  hp[6] = (float)sqrt(bc2);
-  hp[7] = 0.f;
-  state[0] = step;
-  state[1] = s + 1.0;
+  write_hp_row(base_lr * lam, beta1, beta2, eps, wd, step, s, hp, state);
 }
 
 extern "C" int climsr_opt_hparams(double* state, int kind, double lr, double beta1, double beta2, double eps, double wd,
@@ -457,203 +452,126 @@ extern "C" int climsr_opt_hparams(double* state, int kind, double lr, double bet
   return check_launch("opt_hparams");
 }
 
-// torch.optim.AdamW (amsgrad=False) single-tensor semantics in fp32:
-//   p *= 1 - lr*wd; m = b1*m + (1-b1)*g; v = b2*v + (1-b2)*g*g; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
+// The fused update, single-tensor semantics in fp32, of torch.optim.AdamW (amsgrad=False):
+//   p *= 1 - lr*wd; m = m + (G - m)*(1-b1); v = b2*v + (1-b2)*G*G; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
+// and (COUPLED) of torch.optim.Adam, whose weight decay is an L2 term in the gradient instead of the decay of p:
+//   G = g + wd*p; the same m, v and step.
+// The contract: every entry is bit-identical to every other on the same effective gradient -- scaled (G = g * gscale[0],
+// the clip coefficient, rounded to fp32 first; g is only read) against plain on a gradient multiplied beforehand in
+// fp32 or at gscale == 1, with or without the mirror.  So nothing is left to the compiler's contraction: it is off in
+// the element function and in the kernel, and every fused multiply-add is written out.  AdamW's v is
+// fma(1-b2, G*G, b2*v) in the 16-byte body and fma(b2, v, (1-b2)*(G*G)) in the tail loop (VEC selects): the forms the
+// first AdamW kernel was shipped with, kept so that its results do not move (tests/golden/opt_step_parent.npz).
+struct OptScalars {
+  float decay, wd, omb1, omb2, b2, eps, step_size, bc2s;  // decay = 1 - lr*wd (AdamW); omb = 1 - beta
+};
+template <bool COUPLED, bool VEC>
+__device__ __forceinline__ void opt_elem(float& p, float G, float& m, float& v, const OptScalars& s) {
+#pragma clang fp contract(off)
+  if (COUPLED) G = fmaf(s.wd, p, G);
+  m = fmaf(s.omb1, G - m, m);
+  v = (COUPLED || VEC) ? fmaf(s.omb2, G * G, s.b2 * v) : fmaf(s.b2, v, s.omb2 * (G * G));
+  const float q = m / (sqrtf(v) / s.bc2s + s.eps);
+  p = COUPLED ? fmaf(-s.step_size, q, p) : fmaf(s.decay, p, -(s.step_size * q));
+}
+
 // mirror (optional): bf16 copy of the updated p[lo, lo + mn) into mirror[0, mn) -- the MFMA operand of a layer whose
 // weights are read straight from the flat buffer (the discriminator's fc.0), written by this pass instead of a
 // separate fp32 -> bf16 sweep of the same 411 MB.
-__device__ __forceinline__ void adamw_mirror(long i, float v, uint16_t* mirror, long lo, long mn) {
+__device__ __forceinline__ void opt_mirror(long i, float v, uint16_t* mirror, long lo, long mn) {
   if (mirror && i >= lo && i < lo + mn) mirror[i - lo] = f2bf(v);
 }
-__global__ void adamw_kernel(long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                             float* __restrict__ v, const float* __restrict__ hp, uint16_t* __restrict__ mirror = nullptr,
-                             long mlo = 0, long mn = 0) {
+
+template <bool COUPLED, bool SCALED>
+__global__ void opt_step_kernel(long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                float* __restrict__ v, const float* __restrict__ hp, const float* __restrict__ gscale,
+                                uint16_t* __restrict__ mirror, long mlo, long mn) {
+#pragma clang fp contract(off)
   const float lr = hp[0], b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4], step_size = hp[5], bc2s = hp[6];
+  const float c = SCALED ? gscale[0] : 1.f;
+  const OptScalars s = {fmaf(-lr, wd, 1.f), wd, 1.f - b1, 1.f - b2, b2, eps, step_size, bc2s};
   long i4 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i4 + 3 < n) {
     float4 pp = *(float4*)(p + i4), gg = *(const float4*)(g + i4), mm = *(float4*)(m + i4), vv = *(float4*)(v + i4);
     float* P = (float*)&pp; const float* G = (const float*)&gg; float* M = (float*)&mm; float* V = (float*)&vv;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      P[k] *= 1.f - lr * wd;
-      M[k] = M[k] + (G[k] - M[k]) * (1.f - b1);
-      V[k] = V[k] * b2 + G[k] * G[k] * (1.f - b2);
-      P[k] -= step_size * (M[k] / (sqrtf(V[k]) / bc2s + eps));
-    }
+    for (int k = 0; k < 4; ++k) opt_elem<COUPLED, true>(P[k], SCALED ? G[k] * c : G[k], M[k], V[k], s);
     *(float4*)(p + i4) = pp; *(float4*)(m + i4) = mm; *(float4*)(v + i4) = vv;
     if (mirror && i4 >= mlo && i4 + 3 < mlo + mn && ((i4 - mlo) & 3) == 0) {  // 8 B store of 4 bf16
       const uint2 pk = make_uint2((uint32_t)f2bf(P[0]) | ((uint32_t)f2bf(P[1]) << 16), (uint32_t)f2bf(P[2]) | ((uint32_t)f2bf(P[3]) << 16));
       *(uint2*)(mirror + (i4 - mlo)) = pk;
     } else if (mirror) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) adamw_mirror(i4 + k, P[k], mirror, mlo, mn);
+      for (int k = 0; k < 4; ++k) opt_mirror(i4 + k, P[k], mirror, mlo, mn);
     }
   } else {
     for (long i = i4; i < n; ++i) {
-      float pi = p[i] * (1.f - lr * wd);
-      float mi = m[i] + (g[i] - m[i]) * (1.f - b1);
-      float vi = v[i] * b2 + g[i] * g[i] * (1.f - b2);
-      p[i] = pi - step_size * (mi / (sqrtf(vi) / bc2s + eps));
-      m[i] = mi; v[i] = vi;
-      adamw_mirror(i, p[i], mirror, mlo, mn);
+      float pi = p[i], mi = m[i], vi = v[i];
+      opt_elem<COUPLED, false>(pi, SCALED ? g[i] * c : g[i], mi, vi, s);
+      p[i] = pi; m[i] = mi; v[i] = vi;
+      opt_mirror(i, pi, mirror, mlo, mn);
     }
   }
 }
 
+// What every entry asks of its arguments; a mirror window, when given, lies inside the buffer.
+static bool opt_args_ok(int64_t n, const void* p, const void* g, const void* m, const void* v, const void* hp, int64_t mirror_lo,
+                        int64_t mirror_n, const void* mirror) {
+  return p && g && m && v && hp && n > 0 && (!mirror || (mirror_lo >= 0 && mirror_n > 0 && mirror_lo + mirror_n <= n));
+}
+
+// One launch for the five entries below: 4 elements per thread, 256 threads per block; scaled iff gscale is given.
+static int opt_step_launch(const char* name, bool coupled, int64_t n, float* p, const float* g, float* m, float* v, const float* hp,
+                           const float* gscale, int64_t mirror_lo, int64_t mirror_n, uint16_t* mirror, void* stream) {
+  auto kernel = coupled ? (gscale ? opt_step_kernel<true, true> : opt_step_kernel<true, false>)
+                        : (gscale ? opt_step_kernel<false, true> : opt_step_kernel<false, false>);
+  long threads = (n + 3) / 4;
+  hipLaunchKernelGGL(kernel, dim3(ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream, (long)n, p, g, m, v, hp, gscale, mirror,
+                     mirror ? (long)mirror_lo : 0L, mirror ? (long)mirror_n : 0L);
+  return check_launch(name);
+}
+
 extern "C" int climsr_adamw_step(int64_t n, float* p, const float* g, float* m, float* v, const float* hp, void* stream) {
-  if (!p || !g || !m || !v || !hp || n <= 0) {
+  if (!opt_args_ok(n, p, g, m, v, hp, 0, 0, nullptr)) {
     set_error("adamw_step: bad args");
     return CLIMSR_EINVAL;
   }
-  long threads = (n + 3) / 4;
-  hipLaunchKernelGGL(adamw_kernel, dim3(ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream, (long)n, p, g, m, v, hp,
-                     (uint16_t*)nullptr, 0L, 0L);
-  return check_launch("adamw_step");
+  return opt_step_launch("adamw_step", false, n, p, g, m, v, hp, nullptr, 0, 0, nullptr, stream);
 }
 
 extern "C" int climsr_adamw_step_mirror(int64_t n, float* p, const float* g, float* m, float* v, const float* hp, int64_t mirror_lo,
                                         int64_t mirror_n, uint16_t* mirror, void* stream) {
-  if (!p || !g || !m || !v || !hp || n <= 0 || !mirror || mirror_lo < 0 || mirror_n <= 0 || mirror_lo + mirror_n > n) {
+  if (!mirror || !opt_args_ok(n, p, g, m, v, hp, mirror_lo, mirror_n, mirror)) {
     set_error("adamw_step_mirror: bad args");
     return CLIMSR_EINVAL;
   }
-  long threads = (n + 3) / 4;
-  hipLaunchKernelGGL(adamw_kernel, dim3(ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream, (long)n, p, g, m, v, hp, mirror,
-                     (long)mirror_lo, (long)mirror_n);
-  return check_launch("adamw_step_mirror");
-}
-
-// The same update reading G = g * gscale[0] (the gradient-clipping coefficient, a device scalar); g is only read.
-// It must be bit-identical to adamw_kernel on a gradient multiplied beforehand in fp32, so nothing here is left to the
-// compiler's contraction: it is off inside adamw_scaled_elem and every fused multiply-add is written out.  They are the
-// ones hipcc forms in adamw_kernel (its ISA): m = fma(1-b1, G-m, m) and p = fma(1-lr*wd, p, -step_size*q) everywhere,
-// but v = fma(1-b2, G*G, b2*v) in the 16-byte path and v = fma(b2, v, (1-b2)*(G*G)) in the tail loop (VEC selects).
-// tests/test_gpu_gradnorm.py holds the two kernels to bit-identity on both paths; if a compiler change moves
-// adamw_kernel's fusions, those tests say so and this function follows.
-template <bool VEC>
-__device__ __forceinline__ void adamw_scaled_elem(float& p, float g, float c, float& m, float& v, float decay, float omb1,
-                                                  float omb2, float b2, float eps, float step_size, float bc2s) {
-#pragma clang fp contract(off)
-  const float G = g * c;  // rounded to fp32 on its own
-  m = fmaf(omb1, G - m, m);
-  v = VEC ? fmaf(omb2, G * G, b2 * v) : fmaf(b2, v, omb2 * (G * G));
-  p = fmaf(decay, p, -(step_size * (m / (sqrtf(v) / bc2s + eps))));
-}
-__global__ void adamw_scaled_kernel(long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                    float* __restrict__ v, const float* __restrict__ hp, const float* __restrict__ gscale,
-                                    uint16_t* __restrict__ mirror, long mlo, long mn) {
-  const float lr = hp[0], b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4], step_size = hp[5], bc2s = hp[6];
-  const float c = gscale[0];
-  const float decay = fmaf(-lr, wd, 1.f), omb1 = 1.f - b1, omb2 = 1.f - b2;
-  long i4 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (i4 + 3 < n) {
-    float4 pp = *(float4*)(p + i4), gg = *(const float4*)(g + i4), mm = *(float4*)(m + i4), vv = *(float4*)(v + i4);
-    float* P = (float*)&pp; const float* G = (const float*)&gg; float* M = (float*)&mm; float* V = (float*)&vv;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) adamw_scaled_elem<true>(P[k], G[k], c, M[k], V[k], decay, omb1, omb2, b2, eps, step_size, bc2s);
-    *(float4*)(p + i4) = pp; *(float4*)(m + i4) = mm; *(float4*)(v + i4) = vv;
-    if (mirror && i4 >= mlo && i4 + 3 < mlo + mn && ((i4 - mlo) & 3) == 0) {  // 8 B store of 4 bf16
-      const uint2 pk = make_uint2((uint32_t)f2bf(P[0]) | ((uint32_t)f2bf(P[1]) << 16), (uint32_t)f2bf(P[2]) | ((uint32_t)f2bf(P[3]) << 16));
-      *(uint2*)(mirror + (i4 - mlo)) = pk;
-    } else if (mirror) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) adamw_mirror(i4 + k, P[k], mirror, mlo, mn);
-    }
-  } else {
-    for (long i = i4; i < n; ++i) {
-      float pi = p[i], mi = m[i], vi = v[i];
-      adamw_scaled_elem<false>(pi, g[i], c, mi, vi, decay, omb1, omb2, b2, eps, step_size, bc2s);
-      p[i] = pi; m[i] = mi; v[i] = vi;
-      adamw_mirror(i, pi, mirror, mlo, mn);
-    }
-  }
+  return opt_step_launch("adamw_step_mirror", false, n, p, g, m, v, hp, nullptr, mirror_lo, mirror_n, mirror, stream);
 }
 
 extern "C" int climsr_adamw_step_scaled(int64_t n, float* p, const float* g, float* m, float* v, const float* hp,
                                         const float* gscale, int64_t mirror_lo, int64_t mirror_n, uint16_t* mirror, void* stream) {
-  if (!p || !g || !m || !v || !hp || !gscale || n <= 0 ||
-      (mirror && (mirror_lo < 0 || mirror_n <= 0 || mirror_lo + mirror_n > n))) {
+  if (!gscale || !opt_args_ok(n, p, g, m, v, hp, mirror_lo, mirror_n, mirror)) {
     set_error("adamw_step_scaled: bad args");
     return CLIMSR_EINVAL;
   }
-  long threads = (n + 3) / 4;
-  hipLaunchKernelGGL(adamw_scaled_kernel, dim3(ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream, (long)n, p, g, m, v, hp,
-                     gscale, mirror, mirror ? (long)mirror_lo : 0L, mirror ? (long)mirror_n : 0L);
-  return check_launch("adamw_step_scaled");
-}
-
-// torch.optim.Adam (amsgrad=False) with its coupled L2 term, single-tensor semantics in fp32:
-//   G = g + wd*p; m = m + (G - m)*(1-b1); v = b2*v + (1-b2)*G*G; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
-// One element function serves the plain and the scaled entry (SCALED: g is multiplied by the clip coefficient c and
-// rounded to fp32 first), the 16-byte body and the tail alike.  Contraction is off inside it and each fused
-// multiply-add is written out, so the two entries are bit-identical at c == 1 and on a gradient multiplied beforehand
-// in fp32 whatever the compiler would have fused.
-template <bool SCALED>
-__device__ __forceinline__ void adam_elem(float& p, float g, float c, float& m, float& v, float wd, float omb1, float omb2,
-                                          float b2, float eps, float step_size, float bc2s) {
-#pragma clang fp contract(off)
-  float G = SCALED ? g * c : g;
-  G = fmaf(wd, p, G);
-  m = fmaf(omb1, G - m, m);
-  v = fmaf(omb2, G * G, b2 * v);
-  p = fmaf(-step_size, m / (sqrtf(v) / bc2s + eps), p);
-}
-template <bool SCALED>
-__global__ void adam_kernel(long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, const float* __restrict__ hp, const float* __restrict__ gscale,
-                            uint16_t* __restrict__ mirror, long mlo, long mn) {
-  const float b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4], step_size = hp[5], bc2s = hp[6];
-  const float c = SCALED ? gscale[0] : 1.f;
-  const float omb1 = 1.f - b1, omb2 = 1.f - b2;
-  long i4 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (i4 + 3 < n) {
-    float4 pp = *(float4*)(p + i4), gg = *(const float4*)(g + i4), mm = *(float4*)(m + i4), vv = *(float4*)(v + i4);
-    float* P = (float*)&pp; const float* G = (const float*)&gg; float* M = (float*)&mm; float* V = (float*)&vv;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) adam_elem<SCALED>(P[k], G[k], c, M[k], V[k], wd, omb1, omb2, b2, eps, step_size, bc2s);
-    *(float4*)(p + i4) = pp; *(float4*)(m + i4) = mm; *(float4*)(v + i4) = vv;
-    if (mirror && i4 >= mlo && i4 + 3 < mlo + mn && ((i4 - mlo) & 3) == 0) {  // 8 B store of 4 bf16
-      const uint2 pk = make_uint2((uint32_t)f2bf(P[0]) | ((uint32_t)f2bf(P[1]) << 16), (uint32_t)f2bf(P[2]) | ((uint32_t)f2bf(P[3]) << 16));
-      *(uint2*)(mirror + (i4 - mlo)) = pk;
-    } else if (mirror) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) adamw_mirror(i4 + k, P[k], mirror, mlo, mn);
-    }
-  } else {
-    for (long i = i4; i < n; ++i) {
-      float pi = p[i], mi = m[i], vi = v[i];
-      adam_elem<SCALED>(pi, g[i], c, mi, vi, wd, omb1, omb2, b2, eps, step_size, bc2s);
-      p[i] = pi; m[i] = mi; v[i] = vi;
-      adamw_mirror(i, pi, mirror, mlo, mn);
-    }
-  }
-}
-
-static bool adam_args_ok(int64_t n, const void* p, const void* g, const void* m, const void* v, const void* hp, int64_t mirror_lo,
-                         int64_t mirror_n, const void* mirror) {
-  return p && g && m && v && hp && n > 0 && (!mirror || (mirror_lo >= 0 && mirror_n > 0 && mirror_lo + mirror_n <= n));
+  return opt_step_launch("adamw_step_scaled", false, n, p, g, m, v, hp, gscale, mirror_lo, mirror_n, mirror, stream);
 }
 
 extern "C" int climsr_adam_step(int64_t n, float* p, const float* g, float* m, float* v, const float* hp, int64_t mirror_lo,
                                 int64_t mirror_n, uint16_t* mirror, void* stream) {
-  if (!adam_args_ok(n, p, g, m, v, hp, mirror_lo, mirror_n, mirror)) {
+  if (!opt_args_ok(n, p, g, m, v, hp, mirror_lo, mirror_n, mirror)) {
     set_error("adam_step: bad args");
     return CLIMSR_EINVAL;
   }
-  long threads = (n + 3) / 4;
-  hipLaunchKernelGGL(adam_kernel<false>, dim3(ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream, (long)n, p, g, m, v, hp,
-                     (const float*)nullptr, mirror, mirror ? (long)mirror_lo : 0L, mirror ? (long)mirror_n : 0L);
-  return check_launch("adam_step");
+  return opt_step_launch("adam_step", true, n, p, g, m, v, hp, nullptr, mirror_lo, mirror_n, mirror, stream);
 }
 
 extern "C" int climsr_adam_step_scaled(int64_t n, float* p, const float* g, float* m, float* v, const float* hp,
                                        const float* gscale, int64_t mirror_lo, int64_t mirror_n, uint16_t* mirror, void* stream) {
-  if (!adam_args_ok(n, p, g, m, v, hp, mirror_lo, mirror_n, mirror) || !gscale) {
+  if (!gscale || !opt_args_ok(n, p, g, m, v, hp, mirror_lo, mirror_n, mirror)) {
     set_error("adam_step_scaled: bad args");
     return CLIMSR_EINVAL;
   }
-  long threads = (n + 3) / 4;
-  hipLaunchKernelGGL(adam_kernel<true>, dim3(ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream, (long)n, p, g, m, v, hp,
-                     gscale, mirror, mirror ? (long)mirror_lo : 0L, mirror ? (long)mirror_n : 0L);
-  return check_launch("adam_step_scaled");
+  return opt_step_launch("adam_step_scaled", true, n, p, g, m, v, hp, gscale, mirror_lo, mirror_n, mirror, stream);
 }
+

@@ -8,7 +8,7 @@ over --reps calls.  GB/s counts the gradient read once; the ratio is against one
 HBM rate (--hbm-tbs, 6.3 TB/s).  On the discriminator's buffer climsr_adamw_step (mirror variant, as the trainer
 launches it) and climsr_adamw_step_scaled are timed in alternating calls on the same buffers.  Prints one JSON line.
 
-    python tools/perf_gradnorm.py [--reps 50] [--warmup 5]
+    python tools/perf_gradnorm.py [--reps 50] [--warmup 5] [--parent-lib /path/to/another/libclimsr_hip.so]
 """
 import argparse
 import json
@@ -39,6 +39,7 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--hbm-tbs", type=float, default=6.3)
+    ap.add_argument("--parent-lib", default=None, help="another libclimsr_hip.so: time its climsr_adamw_step_mirror beside the tree's")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("perf_gradnorm: no GPU (a timing needs the MI355X)")
@@ -104,6 +105,26 @@ def main():
         r = summary(evs)
         r["GBps"] = round(nbytes / (r["median_ms"] * 1e-3) / 1e9, 1)
         out["adamw_on_discriminator"][k] = r
+    if a.parent_lib:  # the same entry of another build of the library (a parent commit's), alternating with the tree's
+        import ctypes
+
+        other = ctypes.CDLL(a.parent_lib)
+        other.climsr_adamw_step_mirror.restype, other.climsr_adamw_step_mirror.argtypes = _lib.SIGNATURES["climsr_adamw_step_mirror"]
+
+        def parent():
+            assert other.climsr_adamw_step_mirror(n, flat.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), hp.data_ptr(), lo, mn,
+                                                  buf.data_ptr(), s) == 0
+
+        for _ in range(a.warmup):
+            parent()
+            plain()
+        torch.cuda.synchronize()
+        ev = {"parent": [], "tree": []}
+        for _ in range(a.reps):
+            ev["parent"].append(timed(parent))
+            ev["tree"].append(timed(plain))
+        torch.cuda.synchronize()
+        out["adamw_step_mirror_parent_vs_tree"] = {k: summary(evs) for k, evs in ev.items()}
     print(json.dumps(out))
 
 
