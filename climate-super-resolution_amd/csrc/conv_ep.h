@@ -1,4 +1,4 @@
-// Shared by the conv kernel units (conv.hip, conv_fwd.hip, conv_pw.hip, conv_dma.hip): the forward / data-gradient kernel
+// Shared by the conv kernel units (conv_small.hip, conv_fwd.hip, conv_pw.hip, conv_dma.hip): the forward / data-gradient kernel
 // arguments, the coalesced store epilogue (store_tile_lds) with its BatchNorm-partial helpers and the persistent tile
 // walk.  The route and the host-side launcher declarations are in conv_route.h.
 #pragma once

@@ -1,18 +1,22 @@
 // Shared by the conv translation units, host side: the route a forward conv takes (FwdRoute: decided once by fwd_route()
-// in conv.hip from the descriptor and the epilogue alone, no device call) and the launchers of the kernel families that
-// are compiled in units of their own.
+// in conv.hip from the descriptor and the epilogue alone, no device call) and the launchers of the kernel families,
+// each compiled in a unit of its own.
 //
-//   conv.hip      errors and launch plumbing, weight packing, fwd_route() and climsr_conv2d_fwd, the small-shape and
-//                 stride-2 data-gradient kernels, the weight-gradient side
-//   conv_fwd.hip  generic forward / data-gradient kernel (conv_fwd_kernel.h), 16x16 tiles
-//   conv_pw.hip   weights-resident persistent kernel, and the generic kernel's 8x16 tiles
-//   conv_dma.hip  LDS-DMA forms                      conv_wr.hip  register-resident 64 -> 64
+//   conv.hip        errors and launch plumbing, geometry, weight packing, fwd_route() and climsr_conv2d_fwd
+//   conv_small.hip  the shape-specific kernels: n16, co1m, co1, pt, the stride-2 data gradient, the 1 <-> C stencil
+//   conv_fwd.hip    generic forward / data-gradient kernel (conv_fwd_kernel.h), 16x16 tiles
+//   conv_pw.hip     weights-resident persistent kernel, and the generic kernel's 8x16 tiles
+//   conv_dma.hip    LDS-DMA forms                      conv_wr.hip  register-resident 64 -> 64
+//   conv_wgrad.hip  the weight-gradient side (a route of its own, wg_route; from here only FWD_MAXV)
 #pragma once
 #include "conv_ep.h"
 
 namespace climsr {
 constexpr int WPAD = 16;     // k padding of the LDS weight tile rows (kcpad is a multiple of 32)
 constexpr int FWD_MAXV = 8;  // 16 B staging vectors per thread held in registers (prefetch)
+constexpr int N16_TH = 8;    // output rows of a conv_n16_kernel tile
+// 32-channel blocks of conv_n16_kernel's one chunk (its NCB)
+static inline int n16_ncb(int in_c) { return in_c <= 32 ? 1 : (in_c <= 64 ? 2 : 4); }
 
 struct FwdGeom {
   int th, tph, tpw, ccp, kc, kcpad, nchunk, kpk, nt, mw;
@@ -48,8 +52,10 @@ struct FwdRoute {
 // staging vectors (16 B) per thread of conv_fwd_kernel<.., NT, ..>
 constexpr int fwd_mv(int nt) { return nt == 1 ? 6 : (nt == 2 ? 8 : 4); }
 
-// The launchers of the families compiled in units of their own (the others are in conv.hip): each switches on the
-// route's ids to reach the instantiation, CLIMSR_EINVAL (+ set_error) for ids without one.
+// The launchers of the families: each switches on the route's ids to reach the instantiation, CLIMSR_EINVAL
+// (+ set_error) for ids without one.
+int fwd_small_launch(const FwdRoute& r, const FwdArgs& a, hipStream_t s);     // CO1M, CO1, N16, PT (conv_small.hip)
+int fwd_dgrad_s2_launch(const FwdRoute& r, const FwdArgs& a, hipStream_t s);  // conv_small.hip
 int fwd_pw_launch(const FwdRoute& r, const FwdArgs& a, hipStream_t s);        // conv_pw.hip
 int fwd_generic_launch(const FwdRoute& r, const FwdArgs& a, hipStream_t s);   // FWD, DMA (conv_fwd.hip)
 int fwd_rows2_launch(const FwdRoute& r, const FwdArgs& a, hipStream_t s);     // FWD with mw 2 (conv_pw.hip)

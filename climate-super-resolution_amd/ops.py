@@ -253,26 +253,34 @@ class ConvPlan:
     def wgrad(self, x: torch.Tensor, x_cs: int, x_co: int, in_h: int, in_w: int, dz: torch.Tensor, dz_cs: int, n: int,
               workspace: "Workspace", accumulate: bool, up: int = 1) -> None:
         """Weight/bias gradient into self.gw / self.gb (fp32 OIHW)."""
-        lib = _lib.load()
         d = self.wgrad_desc(n, in_h, in_w, x_cs, x_co, up)
-        ns = lib.climsr_conv2d_wgrad_splits(ctypes.byref(d))
-        need = lib.climsr_conv2d_wgrad_workspace(ctypes.byref(d), ns)
-        ws = workspace.get(need, x.device)
         cw = self.cin_w
-        rows_c = need // (ns * (cw * self.ks * self.ks + 1))  # co_rows
-        part = ws
-        bpart = ws[ns * rows_c * cw * self.ks * self.ks:]
-        s = _lib.stream_ptr()
         has_b = self.bias is not None and self.gb is not None
         flops = 2 * self.cin_real * self.cout * self.ks * self.ks * n * d.out_h * d.out_w
         nbytes = n * in_h * in_w * self.cin_real * 2 + n * d.out_h * d.out_w * self.cout * 2 + self.cout * self.cin_real * self.ks ** 2 * 4
-        _run(lib.climsr_conv2d_wgrad_kernel(ctypes.byref(d)).decode() if PROFILER is not None else "", flops,
-             lambda: check(
-            lib.climsr_conv2d_wgrad(ctypes.byref(d), ptr(x), ptr(dz), dz_cs, ptr(part), ptr(bpart) if has_b else None, ns,
-                                    _lib.stream_ptr()), f"conv wgrad {self.name}"), "wgrad " + self.name, nbytes)
-        _launch(f"wgrad reduce {self.name}", lambda: lib.climsr_conv2d_wgrad_reduce(ptr(part), ptr(bpart) if has_b else None, ns, self.cout, self.cin_real, cw,
-                                             self.ks, ptr(self.gw), ptr(self.gb) if has_b else None,
-                                             1 if accumulate else 0, s))
+        ns, part, bpart = _wgrad_slabs(d, cw * self.ks * self.ks, x, dz, dz_cs, workspace, has_b, f"conv wgrad {self.name}",
+                                       "wgrad " + self.name, flops, nbytes)
+        s = _lib.stream_ptr()
+        _launch(f"wgrad reduce {self.name}", lambda: _lib.load().climsr_conv2d_wgrad_reduce(
+            ptr(part), bpart, ns, self.cout, self.cin_real, cw, self.ks, ptr(self.gw), ptr(self.gb) if has_b else None,
+            1 if accumulate else 0, s))
+
+
+def _wgrad_slabs(d, kw: int, x: torch.Tensor, dz: torch.Tensor, dz_cs: int, workspace: "Workspace", has_b: bool, what: str,
+                 label: str, flops: int, nbytes: int):
+    """The split weight-gradient GEMM of descriptor d into the workspace: -> (ns, part, bias-slab pointer or None).
+    The slabs are part[ns][co_rows][kw] then bpart[ns][co_rows] (csrc/conv_wgrad.hip wg_layout), so the library's
+    workspace size ns * co_rows * (kw + 1) gives co_rows and with it the bias slabs' offset -- here and nowhere else."""
+    lib = _lib.load()
+    ns = lib.climsr_conv2d_wgrad_splits(ctypes.byref(d))
+    need = lib.climsr_conv2d_wgrad_workspace(ctypes.byref(d), ns)
+    part = workspace.get(need, x.device)
+    co_rows = need // (ns * (kw + 1))
+    bpart = ptr(part[ns * co_rows * kw:]) if has_b else None
+    _run(lib.climsr_conv2d_wgrad_kernel(ctypes.byref(d)).decode() if PROFILER is not None else "", flops,
+         lambda: check(lib.climsr_conv2d_wgrad(ctypes.byref(d), ptr(x), ptr(dz), dz_cs, ptr(part), bpart, ns, _lib.stream_ptr()), what),
+         label, nbytes)
+    return ns, part, bpart
 
 
 class GroupedWgrad:
@@ -306,22 +314,15 @@ class GroupedWgrad:
 
     def run(self, x: torch.Tensor, x_cs: int, x_co: int, in_h: int, in_w: int, dz: torch.Tensor, dz_cs: int, n: int,
             workspace: "Workspace", accumulate: bool) -> None:
-        lib = _lib.load()
         d = ConvDesc(n, in_h, in_w, self.in_c, x_cs, x_co, 1, 3, 1, 1, in_h, in_w, self.out_c, 0, 0, 8)
-        ns = lib.climsr_conv2d_wgrad_splits(ctypes.byref(d))
-        need = lib.climsr_conv2d_wgrad_workspace(ctypes.byref(d), ns)
-        ws = workspace.get(need, x.device)
-        part = ws
-        bpart = ws[ns * self.out_c * self.in_c * 9:]
-        s = _lib.stream_ptr()
         flops = sum(2 * p.cin_real * p.cout * 9 for p in self.plans) * n * in_h * in_w
         nbytes = n * in_h * in_w * (self.in_c + self.out_c) * 2 + sum(p.cout * p.cin_real * 9 * 4 for p in self.plans)
-        _run(lib.climsr_conv2d_wgrad_kernel(ctypes.byref(d)).decode() if PROFILER is not None else "", flops, lambda: check(
-            lib.climsr_conv2d_wgrad(ctypes.byref(d), ptr(x), ptr(dz), dz_cs, ptr(part), ptr(bpart), ns, _lib.stream_ptr()),
-            f"grouped wgrad {self.name}"), "wgrad " + self.name, nbytes)
+        ns, part, bpart = _wgrad_slabs(d, self.in_c * 9, x, dz, dz_cs, workspace, True, f"grouped wgrad {self.name}",
+                                       "wgrad " + self.name, flops, nbytes)
+        s = _lib.stream_ptr()
         tab = self._table(x.device)
-        _launch(f"grouped wgrad reduce {self.name}", lambda: lib.climsr_conv2d_wgrad_reduce_rows(ptr(part), ptr(bpart), ns, self.out_c, self.in_c * 9, 3, ptr(tab),
-                                                  len(self.plans), self.max_elems, 1 if accumulate else 0, s))
+        _launch(f"grouped wgrad reduce {self.name}", lambda: _lib.load().climsr_conv2d_wgrad_reduce_rows(
+            ptr(part), bpart, ns, self.out_c, self.in_c * 9, 3, ptr(tab), len(self.plans), self.max_elems, 1 if accumulate else 0, s))
 
 
 class Workspace:
