@@ -457,7 +457,12 @@ static void pick_generic(const ClimsrConvDesc* d, bool bias, const ClimsrEpilogu
   const bool r1 = ep->res1 != nullptr, r2 = ep->res2 != nullptr, aux = ep->aux != nullptr, bwd = ep->act == 3 || ep->act == 4;
   const bool al8 = (d->out_c & 7) == 0 && ((d->out_cstride | d->out_coff) & 7) == 0;
   const bool r1al8 = ((ep->res1_cstride | ep->res1_coff) & 7) == 0;
-  const int plain = plain_ep(d, bias, ep);
+  // the max-pool epilogue (down2 == 2, fwd_route has checked its operands) is EP 3's conv: picked as that one, then
+  // EP 11 where the LDS-DMA kernel takes it; left on any other kernel, fwd_route refuses it
+  const bool pool = ep->down2 == 2;
+  ClimsrEpilogue unpooled = *ep;
+  unpooled.down2 = 0;
+  const int plain = plain_ep(d, bias, pool ? &unpooled : ep);
   r->family = FAM_FWD; r->mw = g.mw; r->nt = g.nt;
   // (a stride-2 data gradient that only dgrad_s2's operand-size test turned away is still promised its partial rows)
   r->parts = bz && d->up == -2 && plain == 8 && dgrad_s2_shape(d, bias, ep);
@@ -500,7 +505,10 @@ static void pick_generic(const ClimsrConvDesc* d, bool bias, const ClimsrEpilogu
     // the GAN step than the two-workgroups-per-CU form (its chunk-0 latency and epilogue are not hidden in a single
     // round)
     const bool fits = (r->ep == 9 || r->ep == 10) ? d->out_h % DMA_TH == 0 : (d->out_h % DMA_TH == 0 || d->out_h >= 3 * DMA_TH);
-    if (r->ep != 1 && r->ep != 2 && !ep->down2 && fits) {
+    // pooled: whole 64-channel blocks only (the direct epilogues store all 64 channels of a block)
+    const bool pooled = pool && r->ep == 3 && ep->act == 2 && d->out_c % 64 == 0;
+    if (r->ep != 1 && r->ep != 2 && (!ep->down2 || pooled) && fits) {
+      if (pooled) r->ep = 11;
       r->family = FAM_DMA;
       r->tiles_y = ceil_div(d->out_h, DMA_TH);
       r->xgrp = conv_xcd_group(r->ncob, (long)64 * g.kpk * 2);
@@ -593,7 +601,26 @@ static int fwd_route(const ClimsrConvDesc* d, bool bias, const ClimsrEpilogue* e
               d->in_coff, d->cc, d->up, d->stride, d->ks);
     return CLIMSR_EINVAL;
   }
-  if (ep->down2 && (ep->res2 || ep->res_f32 || bias || ep->act == 1 || ep->act == 2 || (ep->res1 && ep->act < 3) ||
+  if (ep->down2 == 2) {  // bias + ReLU + 2x2 max-pool, only the pooled bf16 map stored (an inference-only forward)
+    if (ep->act != 2 || !bias) {
+      set_error("conv2d_fwd: max-pool epilogue (down2 = 2) needs a bias and ReLU (act 2), got act %d%s", ep->act, bias ? "" : ", no bias");
+      return CLIMSR_EINVAL;
+    }
+    if (ep->out_mode != 0) {
+      set_error("conv2d_fwd: max-pool epilogue (down2 = 2) stores bf16 only (out_mode %d)", ep->out_mode);
+      return CLIMSR_EINVAL;
+    }
+    if (ep->res1 || ep->res2 || ep->res_f32 || ep->aux || ep->bn_part || ep->ch_part) {
+      set_error("conv2d_fwd: max-pool epilogue (down2 = 2) takes no residual, aux output, BatchNorm partials or channel sums");
+      return CLIMSR_EINVAL;
+    }
+    if ((d->out_h & 1) || (d->out_w & 1) || d->up != 1 || d->stride != 1) {
+      set_error("conv2d_fwd: max-pool epilogue (down2 = 2) needs an even output size (%d x %d), up 1 and stride 1 (up %d, stride %d)",
+                d->out_h, d->out_w, d->up, d->stride);
+      return CLIMSR_EINVAL;
+    }
+  }
+  if (ep->down2 && ep->down2 != 2 && (ep->res2 || ep->res_f32 || bias || ep->act == 1 || ep->act == 2 || (ep->res1 && ep->act < 3) ||
                     (d->out_h & 1) || (d->out_w & 1))) {
     set_error("conv2d_fwd: down2 epilogue: no bias / forward activation / residual (act 3/4 mask only), even output size");
     return CLIMSR_EINVAL;
@@ -603,7 +630,12 @@ static int fwd_route(const ClimsrConvDesc* d, bool bias, const ClimsrEpilogue* e
     return CLIMSR_EINVAL;
   }
   const int pick = fwd_pick(d, bias, ep, r);
-  if (ep->ch_part && !(pick == PICK_OK && r->family == FAM_WR && (r->ep == 3 || r->ep == 4))) {
+  if (ep->down2 == 2 && !(pick == PICK_OK && ((r->family == FAM_WR && r->ep == 5) || (r->family == FAM_DMA && r->ep == 11)))) {
+    set_error("conv2d_fwd: max-pool epilogue (down2 = 2) only from the 64 -> 64 register-resident conv and the LDS-DMA conv "
+              "(climsr_conv2d_fwd_kernel names the kernel, or nothing); run the conv and climsr_maxpool2_bf16 instead");
+    return CLIMSR_EINVAL;
+  }
+  if (ep->ch_part &&!(pick == PICK_OK && r->family == FAM_WR && (r->ep == 3 || r->ep == 4))) {
     set_error("conv2d_fwd: per-tile channel sums only from the 64 -> 64 3x3 register-resident conv "
               "(climsr_conv2d_fwd_ch_parts)");
     return CLIMSR_EINVAL;

@@ -114,13 +114,16 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_dma_kernel(FwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool BN = EP == 9 || EP == 10;
   // epilogues with a fixed store count per lane (dma_store_half), so the wait for the next item's chunk 0 skips them
-  constexpr bool CNT = EP == 1 || EP == 2 || EP == 3 || EP == 6 || EP == 7 || EP == 8;
+  constexpr bool CNT = EP == 1 || EP == 2 || EP == 3 || EP == 6 || EP == 7 || EP == 8 || EP == 11;
   // EP 3 / 6 / 8 store straight from the accumulators (16 stores per lane and item): no LDS staging, no barrier --
   // VGG 256 ch @64^2 295 -> 277 us, 512 ch @32^2 263 -> 249 us against the staged form (tools/perf_diag.py, r04dd).
   // (EP 9 the same way, with its BatchNorm sums xor-shuffled over the pixel columns, measured 9 % slower in the GAN
   // step, r04h: it keeps the staged tile)
-  constexpr bool DIRECT = EP == 3 || EP == 6 || EP == 8;
-  constexpr int NST_ITEM = DIRECT ? 16 : 2 * DmaEp<CNT ? EP : 8>::NSTORE;
+  // EP 11 = EP 3's bias + ReLU followed by a 2x2 max-pool (ClimsrEpilogue.down2 == 2): only the pooled map is
+  // stored, 4 stores per lane and item
+  constexpr bool POOL = EP == 11;
+  constexpr bool DIRECT = EP == 3 || EP == 6 || EP == 8 || POOL;
+  constexpr int NST_ITEM = POOL ? 4 : DIRECT ? 16 : 2 * DmaEp<CNT ? EP : 8>::NSTORE;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, col = lane & 15;
   const int wvu = __builtin_amdgcn_readfirstlane(wave);
   const int ntile = a.tiles_x * a.tiles_y * a.n, ncob = (a.out_c + 63) / 64;  // = the host's packed-row blocks
@@ -309,7 +312,35 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_dma_kernel(FwdArgs a) {
         out[a.out_c + co0 + lane] = (double)tq;
       }
       return;
-    } else if (DIRECT) {
+    } else if constexpr (POOL) {
+      // lane (col, g) holds channels co0 + 16 t + 4 g .. + 3 of pixel (oy0 + 4 wave + m, ox0 + col), and the wave's
+      // 4 x 16 pixels are 2 x 8 whole windows (out_h, out_w even; oy0 + 4 wave a multiple of 4): rows pair in the lane's
+      // registers, columns with lane ^ 1 by DPP; the even column's lane finishes rows 0 / 1, the odd column's rows
+      // 2 / 3 -- 4 stores of 8 B per lane and item into the pooled buffer, issued unconditionally.  Max over the raw
+      // accumulators first: bias, ReLU and the bf16 rounding are monotone, so the bits are those of conv + maxpool2.
+      // A window is wholly inside the image or wholly outside it (BUF_OOB): no out-of-image value is ever compared in.
+      const __amdgpu_buffer_rsrc_t ry = buf_rsrc(a.y, (uint32_t)((long)a.n * (a.out_h >> 1) * (a.out_w >> 1) * a.out_cs * 2));
+      const int odd = col & 1, oy = oy0 + wave * 4 + 2 * odd, ox = ox0 + col;
+      const uint32_t pix = ((uint32_t)nimg * (uint32_t)(a.out_h >> 1) + (uint32_t)(oy >> 1)) * (uint32_t)(a.out_w >> 1) + (uint32_t)(ox >> 1);
+      const uint32_t pb = (oy < a.out_h && ox < a.out_w) ? (pix * (uint32_t)a.out_cs + (uint32_t)(a.out_co + co0 + 4 * g)) * 2u : BUF_OOB;
+      float4 bb[4];  // (loaded before the first store, as the un-pooled epilogue does)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) bb[t] = *(const float4*)(a.bias + co0 + 16 * t + 4 * g);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const float bt[4] = {bb[t].x, bb[t].y, bb[t].z, bb[t].w};
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float r01 = fmaxf(acc[0][t][i], acc[1][t][i]), r23 = fmaxf(acc[2][t][i], acc[3][t][i]);
+          v[i] = act_apply(fmaxf(odd ? r23 : r01, quad_swap1(odd ? r01 : r23)) + bt[i], 2, 0.f);
+        }
+        const bf16x2 p0 = {(__bf16)v[0], (__bf16)v[1]}, p1 = {(__bf16)v[2], (__bf16)v[3]};
+        typedef uint32_t v2u32_t __attribute__((ext_vector_type(2)));
+        const v2u32_t pk = {__builtin_bit_cast(uint32_t, p0), __builtin_bit_cast(uint32_t, p1)};
+        __builtin_amdgcn_raw_buffer_store_b64(pk, ry, pb == BUF_OOB ? BUF_OOB : pb + (uint32_t)(32 * t), 0, 0);
+      }
+    } else if constexpr (DIRECT) {
       // lane (col, g) holds channels co0 + 16 t + 4 g .. + 3 of pixel (oy0 + 4 wave + m, ox0 + col): bias / activation,
       // bf16, one 8 B store per (m, t) -- 16 per lane per item, issued unconditionally (out-of-range offsets drop)
       const __amdgpu_buffer_rsrc_t ry = buf_rsrc(a.y, (uint32_t)((long)a.n * a.out_h * a.out_w * a.out_cs * 2));
@@ -382,6 +413,7 @@ int fwd_dma_launch(int ep, const FwdArgs& a, int ncob, hipStream_t s) {
   case E: k = rf ? conv_fwd_dma_kernel<E, true> : conv_fwd_dma_kernel<E, false>; break;
   switch (ep) {
     DMA_EP(0) DMA_EP(3) DMA_EP(4) DMA_EP(6) DMA_EP(7) DMA_EP(8) DMA_EP(9) DMA_EP(10)
+    case 11: k = conv_fwd_dma_kernel<11, false>; break;  // (its route has no residual, so no fp32 one)
     default: set_error("conv2d_fwd: no LDS-DMA kernel for epilogue %d", ep); return CLIMSR_EINVAL;
   }
 #undef DMA_EP

@@ -334,7 +334,7 @@ __device__ __forceinline__ void bn_tile_partials(const FwdArgs& a, float* ssum, 
 
 
 // LDS-DMA conv (conv_dma.hip): 32-row output tiles; launches conv_fwd_dma_kernel<ep, a.res_f32 != 0> (EP 0, 1, 2, 3,
-// 4, 6, 7, 8) over the grid a.xgrp / a.tiles_y describe; CLIMSR_EINVAL for an EP it has no kernel for
+// 4, 6, 7, 8, 9, 10, 11) over the grid a.xgrp / a.tiles_y describe; CLIMSR_EINVAL for an EP it has no kernel for
 namespace climsr {
 constexpr int DMA_TH = 32;
 int fwd_dma_launch(int ep, const FwdArgs& a, int ncob, hipStream_t s);

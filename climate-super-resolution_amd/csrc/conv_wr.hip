@@ -69,10 +69,11 @@ __device__ __forceinline__ float wr_axpby(bool fused, float x, float alpha, floa
 // and hipcc kept a uniform branch tree around each of the 64 elements of a lane
 template <int EP, int ACT>
 __global__ __launch_bounds__(256, 1) void conv_wr_kernel(WrArgs a) {
-  static_assert(EP == 2 ? (ACT == 3 || ACT == 4) : EP == 1 ? ACT == 0 : (ACT >= 0 && ACT <= 2), "conv_wr_ep()'s pairs");
+  static_assert(EP == 2 ? (ACT == 3 || ACT == 4) : EP == 1 ? ACT == 0 : EP == 5 ? ACT == 2 : (ACT >= 0 && ACT <= 2),
+                "conv_wr_ep()'s pairs");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // vector-memory operations of one epilogue (loads + stores), fixed per lane
-  constexpr int NEPI = EP == 0 ? 16 : (EP == 3 || EP == 4 ? 17 : 32);
+  // vector-memory operations of one epilogue (loads + stores), fixed per lane (EP 5: the 4 pooled stores)
+  constexpr int NEPI = EP == 0 ? 16 : EP == 5 ? 4 : (EP == 3 || EP == 4 ? 17 : 32);
   constexpr bool SUMS = EP == 3 || EP == 4;  // per-tile channel sums (EP 3: fp32 out, EP 4: bf16 out)
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, col = lane & 15;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -197,77 +198,103 @@ __global__ __launch_bounds__(256, 1) void conv_wr_kernel(WrArgs a) {
     // every lane issues the same number of loads / stores (out-of-range offsets are dropped)
     const int nimg = ni, oy0 = ty * WR_TR, ox0 = tx * WR_TC;
     const int ox = ox0 + col;
-    uint32_t off[4];
-    uint2 rv[4][4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const int oy = oy0 + m;
-      const bool ok = oy < a.out_h && ox < a.out_w;
-      const long pix = ((long)nimg * a.out_h + oy) * a.out_w + ox;
-      off[m] = ok ? (uint32_t)((pix * a.out_cs + a.out_co + 4 * g) * (EP == 3 ? 4 : 2)) : BUF_OOB;
-      if constexpr (EP == 1 || EP == 2) {
-        const uint32_t ro = ok ? (uint32_t)((pix * a.r1_cs + a.r1_co + 4 * g) * 2) : BUF_OOB;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const auto v = __builtin_amdgcn_raw_buffer_load_b64(rr, ro == BUF_OOB ? BUF_OOB : ro + (uint32_t)(t * 32), 0, 0);
-          rv[m][t] = make_uint2(v[0], v[1]);
-        }
-      }
-    }
-    float csum[4][4] = {};  // EP 3 / 4: this lane's channel sums over its 4 pixels (rows)
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
+    if constexpr (EP == 5) {
+      // bias + ReLU + 2x2 max-pool (out_h, out_w even): the tile holds 2 x 8 whole windows.  Rows pair in the lane's
+      // own registers, columns with lane ^ 1 (one DPP quad permute per value): the even column's lane finishes the
+      // window of rows 0 / 1, the odd column's that of rows 2 / 3, so every lane stores 4 x 8 B into the pooled buffer
+      // (a.y_bytes describes that one).  The max is taken over the raw accumulators: bias add, ReLU and the bf16
+      // rounding are monotone, so the result is the max of the four rounded values, bit for bit.  A window is wholly
+      // inside the image or wholly outside it (then BUF_OOB): no out-of-image accumulator enters a stored value.
+      const int odd = col & 1;
+      const bool ok = oy0 + 2 * odd < a.out_h && ox < a.out_w;
+      const long pix = ((long)nimg * (a.out_h >> 1) + (oy0 >> 1) + odd) * (a.out_w >> 1) + (ox >> 1);
+      const uint32_t po = ok ? (uint32_t)((pix * a.out_cs + a.out_co + 4 * g) * 2) : BUF_OOB;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         float v[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          float x = acc[m][t][i] + bias[t][i];
-          if constexpr (EP == 2) {
-            const uint32_t w = i < 2 ? rv[m][t].x : rv[m][t].y;
-            const float r = __uint_as_float((i & 1) ? (w & 0xFFFF0000u) : (w << 16));
-            x = r > 0.f ? x : (ACT == 3 ? x * a.slope : 0.f);
-          } else {
-            if constexpr (ACT == 1) x = x > 0.f ? x : x * a.slope;
-            else if constexpr (ACT == 2) x = x > 0.f ? x : 0.f;
-            if constexpr (EP == 1) {
-              const uint32_t w = i < 2 ? rv[m][t].x : rv[m][t].y;
-              const float r = __uint_as_float((i & 1) ? (w & 0xFFFF0000u) : (w << 16));
-              x = wr_axpby(i < 3, x, a.alpha1, a.beta1, r);
-            }
-          }
-          v[i] = x;
+          const float r01 = fmaxf(acc[0][t][i], acc[1][t][i]), r23 = fmaxf(acc[2][t][i], acc[3][t][i]);
+          const float x = fmaxf(odd ? r23 : r01, quad_swap1(odd ? r01 : r23)) + bias[t][i];
+          v[i] = x > 0.f ? x : 0.f;
         }
-        if constexpr (EP == 3) {
-          const v4u32 pk = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
-          __builtin_amdgcn_raw_buffer_store_b128(pk, yr, off[m] == BUF_OOB ? BUF_OOB : off[m] + (uint32_t)(t * 64), 0, 0);
-          if (off[m] != BUF_OOB) {
+        const bf16x2 p0 = {(__bf16)v[0], (__bf16)v[1]}, p1 = {(__bf16)v[2], (__bf16)v[3]};
+        const v2u32 pk = {__builtin_bit_cast(uint32_t, p0), __builtin_bit_cast(uint32_t, p1)};
+        __builtin_amdgcn_raw_buffer_store_b64(pk, yr, po == BUF_OOB ? BUF_OOB : po + (uint32_t)(t * 32), 0, 0);
+      }
+    } else {
+      uint32_t off[4];
+      uint2 rv[4][4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) csum[t][i] += v[i];
-          }
-        } else {
-          const bf16x2 p0 = {(__bf16)v[0], (__bf16)v[1]}, p1 = {(__bf16)v[2], (__bf16)v[3]};
-          const v2u32 pk = {__builtin_bit_cast(uint32_t, p0), __builtin_bit_cast(uint32_t, p1)};
-          __builtin_amdgcn_raw_buffer_store_b64(pk, yr, off[m] == BUF_OOB ? BUF_OOB : off[m] + (uint32_t)(t * 32), 0, 0);
-          if (EP == 4 && off[m] != BUF_OOB) {
+      for (int m = 0; m < 4; ++m) {
+        const int oy = oy0 + m;
+        const bool ok = oy < a.out_h && ox < a.out_w;
+        const long pix = ((long)nimg * a.out_h + oy) * a.out_w + ox;
+        off[m] = ok ? (uint32_t)((pix * a.out_cs + a.out_co + 4 * g) * (EP == 3 ? 4 : 2)) : BUF_OOB;
+        if constexpr (EP == 1 || EP == 2) {
+          const uint32_t ro = ok ? (uint32_t)((pix * a.r1_cs + a.r1_co + 4 * g) * 2) : BUF_OOB;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) csum[t][i] += v[i];
+          for (int t = 0; t < 4; ++t) {
+            const auto v = __builtin_amdgcn_raw_buffer_load_b64(rr, ro == BUF_OOB ? BUF_OOB : ro + (uint32_t)(t * 32), 0, 0);
+            rv[m][t] = make_uint2(v[0], v[1]);
           }
         }
       }
-    if constexpr (SUMS) {
-      // per-tile channel sums: the lanes' column sums transposed through this wave's LDS corner ([channel][17]: both
-      // passes conflict-free), then lane l adds channel l's 16 columns in order and stores it (one 4 B store a lane;
-      // the xor-shuffle tree it replaces took 64 ds_bpermute per lane).  Wave-private: LDS order within the wave suffices.
-      float* red = (float*)(smem + WR_LDS) + wv * (WR_RED / 4);
+      float csum[4][4] = {};  // EP 3 / 4: this lane's channel sums over its 4 pixels (rows)
 #pragma unroll
-      for (int t = 0; t < 4; ++t)
+      for (int m = 0; m < 4; ++m)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) red[(16 * t + 4 * g + i) * 17 + col] = csum[t][i];
-      float cs = 0.f;
+        for (int t = 0; t < 4; ++t) {
+          float v[4];
 #pragma unroll
-      for (int c = 0; c < 16; ++c) cs += red[lane * 17 + c];
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(cs), pr, (uint32_t)((T * 64 + lane) * 4), 0, 0);
+          for (int i = 0; i < 4; ++i) {
+            float x = acc[m][t][i] + bias[t][i];
+            if constexpr (EP == 2) {
+              const uint32_t w = i < 2 ? rv[m][t].x : rv[m][t].y;
+              const float r = __uint_as_float((i & 1) ? (w & 0xFFFF0000u) : (w << 16));
+              x = r > 0.f ? x : (ACT == 3 ? x * a.slope : 0.f);
+            } else {
+              if constexpr (ACT == 1) x = x > 0.f ? x : x * a.slope;
+              else if constexpr (ACT == 2) x = x > 0.f ? x : 0.f;
+              if constexpr (EP == 1) {
+                const uint32_t w = i < 2 ? rv[m][t].x : rv[m][t].y;
+                const float r = __uint_as_float((i & 1) ? (w & 0xFFFF0000u) : (w << 16));
+                x = wr_axpby(i < 3, x, a.alpha1, a.beta1, r);
+              }
+            }
+            v[i] = x;
+          }
+          if constexpr (EP == 3) {
+            const v4u32 pk = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+            __builtin_amdgcn_raw_buffer_store_b128(pk, yr, off[m] == BUF_OOB ? BUF_OOB : off[m] + (uint32_t)(t * 64), 0, 0);
+            if (off[m] != BUF_OOB) {
+#pragma unroll
+              for (int i = 0; i < 4; ++i) csum[t][i] += v[i];
+            }
+          } else {
+            const bf16x2 p0 = {(__bf16)v[0], (__bf16)v[1]}, p1 = {(__bf16)v[2], (__bf16)v[3]};
+            const v2u32 pk = {__builtin_bit_cast(uint32_t, p0), __builtin_bit_cast(uint32_t, p1)};
+            __builtin_amdgcn_raw_buffer_store_b64(pk, yr, off[m] == BUF_OOB ? BUF_OOB : off[m] + (uint32_t)(t * 32), 0, 0);
+            if (EP == 4 && off[m] != BUF_OOB) {
+#pragma unroll
+              for (int i = 0; i < 4; ++i) csum[t][i] += v[i];
+            }
+          }
+        }
+      if constexpr (SUMS) {
+        // per-tile channel sums: the lanes' column sums transposed through this wave's LDS corner ([channel][17]: both
+        // passes conflict-free), then lane l adds channel l's 16 columns in order and stores it (one 4 B store a lane;
+        // the xor-shuffle tree it replaces took 64 ds_bpermute per lane).  Wave-private: LDS order within the wave suffices.
+        float* red = (float*)(smem + WR_LDS) + wv * (WR_RED / 4);
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) red[(16 * t + 4 * g + i) * 17 + col] = csum[t][i];
+        float cs = 0.f;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) cs += red[lane * 17 + c];
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(cs), pr, (uint32_t)((T * 64 + lane) * 4), 0, 0);
+      }
     }
     if (Tn >= a.ntiles) break;
     T = Tn;
@@ -282,18 +309,22 @@ namespace climsr {
 
 // the conv_wr epilogue for (d, ep), or -1 when the conv is not this kernel's: 0 bias / activation, bf16 out; 1 + bf16
 // residual; 2 activation backward from the stored activation (no bias); 3 bias / activation, fp32 out (+ per-tile
-// channel sums); 4 bias / activation, bf16 out + per-tile channel sums (of the fp32 values).
+// channel sums); 4 bias / activation, bf16 out + per-tile channel sums (of the fp32 values); 5 bias + ReLU + 2x2
+// max-pool, bf16 out at half the size (ClimsrEpilogue.down2 == 2).
 int conv_wr_ep(const ClimsrConvDesc* d, const ClimsrEpilogue* ep, bool bias) {
   const bool res = ep->res1 != nullptr;
   int epk = -1;
-  if (ep->out_mode == 0 && !res && ep->act >= 0 && ep->act <= 2) epk = ep->ch_part ? 4 : 0;
+  if (ep->down2 == 2) {
+    const bool even = !((d->out_h | d->out_w) & 1);
+    epk = (ep->out_mode == 0 && !res && ep->act == 2 && bias && !ep->ch_part && d->up == 1 && even) ? 5 : -1;
+  } else if (ep->out_mode == 0 && !res && ep->act >= 0 && ep->act <= 2) epk = ep->ch_part ? 4 : 0;
   else if (ep->out_mode == 0 && res && ep->act == 0 && !(ep->res_f32 & 1)) epk = 1;
   else if (ep->out_mode == 0 && res && (ep->act == 3 || ep->act == 4) && !bias && !(ep->res_f32 & 1)) epk = 2;
   else if (ep->out_mode == 1 && !res && ep->act >= 0 && ep->act <= 2) epk = 3;
   const long opx = (long)d->n * d->out_h * d->out_w;
   if (epk < 0 || (ep->ch_part && epk != 3 && epk != 4) || d->in_c != 64 || d->out_c != 64 || d->cc != 64 || d->ks != 3 || d->stride != 1 ||
       d->pad != 1 || (d->up != 1 && d->up != 2) || d->out_h != d->in_h * d->up || d->out_w != d->in_w * d->up ||
-      d->in_cstride % 8 || d->in_coff % 8 || (d->out_cstride | d->out_coff) & 3 || ep->down2 || ep->res2 || ep->aux ||
+      d->in_cstride % 8 || d->in_coff % 8 || (d->out_cstride | d->out_coff) & 3 || (ep->down2 && epk != 5) || ep->res2 || ep->aux ||
       ep->bn_part || (res && ((ep->res1_cstride | ep->res1_coff) & 3)) ||
       (long)d->n * d->in_h * d->in_w * d->in_cstride * 2 >= (1L << 31) ||
       opx * d->out_cstride * (epk == 3 ? 4 : 2) >= (1L << 31) || (res && opx * ep->res1_cstride * 2 >= (1L << 31)) ||
@@ -319,11 +350,11 @@ int conv_wr_launch(int epk, const ClimsrConvDesc* d, const ClimsrEpilogue* ep, c
   a.tiles_x = ceil_div(d->out_w, WR_TC); a.tiles_y = ceil_div(d->out_h, WR_TR);
   a.ntiles = a.tiles_x * a.tiles_y * d->n;
   a.x_bytes = (uint32_t)((long)d->n * d->in_h * d->in_w * d->in_cstride * 2);
-  a.y_bytes = (uint32_t)(opx * d->out_cstride * (epk == 3 ? 4 : 2));
+  a.y_bytes = (uint32_t)((epk == 5 ? opx / 4 : opx) * d->out_cstride * (epk == 3 ? 4 : 2));  // EP 5: the pooled buffer
   a.r1_bytes = res ? (uint32_t)(opx * ep->res1_cstride * 2) : 0u;
   const int ncu = device_cus();
   const int grid = std::min(ceil_div(a.ntiles, 4), ncu);
-  // (conv_wr_ep() admits act 0..2 for EP 0 / 3 / 4, 0 for EP 1, 3 / 4 for EP 2)
+  // (conv_wr_ep() admits act 0..2 for EP 0 / 3 / 4, 0 for EP 1, 3 / 4 for EP 2, 2 for EP 5)
   void (*k)(WrArgs) = nullptr;
 #define WR_ACT3(E) (a.act == 1 ? conv_wr_kernel<E, 1> : a.act == 2 ? conv_wr_kernel<E, 2> : conv_wr_kernel<E, 0>)
   switch (epk) {
@@ -331,6 +362,7 @@ int conv_wr_launch(int epk, const ClimsrConvDesc* d, const ClimsrEpilogue* ep, c
     case 1: k = conv_wr_kernel<1, 0>; break;
     case 2: k = a.act == 3 ? conv_wr_kernel<2, 3> : conv_wr_kernel<2, 4>; break;
     case 3: k = WR_ACT3(3); break;
+    case 5: k = conv_wr_kernel<5, 2>; break;
     default: k = WR_ACT3(4); break;
   }
 #undef WR_ACT3

@@ -3,7 +3,9 @@
 VGG19 ``features[:35]`` (conv1_1 .. conv5_4, the last without ReLU) applied to the 1->3 channel
 repeat of both images, L1 between the feature maps, all without gradient (F7: the loss adds to
 the value only).  Both images run as ONE batch through native implicit-GEMM convs with fused
-bias+ReLU epilogues and MaxPool2d(2,2) kernels; the L1 is a deterministic bf16 reduction.
+bias+ReLU epilogues; the four MaxPool2d(2,2) run inside the epilogue of the conv before them (only the
+pooled map is written: nothing reads the un-pooled one, the loss has no backward) where that conv's kernel
+has the pooled epilogue, as a MaxPool2d kernel after it elsewhere; the L1 is a deterministic bf16 reduction.
 
 Weights: ``vgg19(pretrained=True)`` (perceptual.py:15) downloads ImageNet weights, impossible
 offline; the module is built with the reference's parameter names (``loss_network.{i}.weight``)
@@ -38,8 +40,10 @@ def _vgg19_features_35() -> nn.Sequential:
 class PerceptualLoss(nn.Module):
     """Assumes input images of shape Nx1xHxW (perceptual.py:8-10)."""
 
-    def __init__(self, deterministic_init: bool = True):
+    def __init__(self, deterministic_init: bool = True, fuse_pool: bool = True):
+        """fuse_pool=False keeps every pool a kernel of its own (conv + ops.maxpool2): the same bits, for comparison."""
         super().__init__()
+        self.fuse_pool = fuse_pool
         loss_network = _vgg19_features_35().eval()
         if deterministic_init:
             shapes = {k: tuple(v.shape) for k, v in loss_network.state_dict().items()}
@@ -50,6 +54,7 @@ class PerceptualLoss(nn.Module):
         self.loss_network = loss_network
         self._plans = None
         self._dev = None
+        self._fused = {}  # (n, h, w) -> per conv: does its epilogue pool
 
     def _build(self, dev):
         plans = []
@@ -66,12 +71,34 @@ class PerceptualLoss(nn.Module):
                 plans.append((p, relu, pool))
         self._plans = plans
         self._dev = dev
+        self._fused = {}
         self._version = sum(int(p.weight._version) for p, _r, _q in plans)
+
+    def _pool_fused(self, n: int, h: int, w: int):
+        """Per conv, whether its kernel pools in the epilogue at this input shape: asked of the dispatch once per shape
+        (ConvPlan.pool2_ok, no launch).  The rest -- tiles too small for the LDS-DMA conv -- keep conv + ops.maxpool2."""
+        key = (n, h, w)
+        if key not in self._fused:
+            out, cs = [], 8
+            for p, relu, pool in self._plans:
+                ok = self.fuse_pool and relu and pool and h % 2 == 0 and w % 2 == 0 and p.pool2_ok(cs, 0, h, w, n, p.cout)
+                out.append(ok)
+                cs = p.cout
+                if pool:
+                    h, w = h // 2, w // 2
+            self._fused[key] = out
+        return self._fused[key]
 
     def features(self, x3: torch.Tensor, n: int, h: int, w: int) -> torch.Tensor:
         """x3: NHWC bf16 [n,h,w,8] with channels 0..2 = the image.  Returns conv5_4 features (bf16)."""
         a, cs = x3, 8
-        for p, relu, pool in self._plans:
+        for (p, relu, pool), fused in zip(self._plans, self._pool_fused(n, h, w)):
+            if fused:  # conv + bias + ReLU + MaxPool2d(2, 2) in one kernel
+                h2, w2 = h // 2, w // 2
+                yp = torch.empty((n, h2, w2, p.cout), dtype=torch.bfloat16, device=x3.device)
+                p.fwd(a, cs, 0, h, w, yp, p.cout, 0, n, act=ACT_RELU, out_mode=OUT_BF16, pool2=True)
+                a, cs, h, w = yp, p.cout, h2, w2
+                continue
             y = torch.empty((n, h, w, p.cout), dtype=torch.bfloat16, device=x3.device)
             p.fwd(a, cs, 0, h, w, y, p.cout, 0, n, act=ACT_RELU if relu else ACT_NONE, out_mode=OUT_BF16)
             a, cs = y, p.cout

@@ -64,7 +64,15 @@ typedef struct ClimsrEpilogue {
   int32_t res2_cstride, res2_coff;
   int32_t out_mode;             /* 0 bf16 store, 1 f32 store, 2 f32 accumulate (+=) */
   int32_t down2;                /* 1: sum 2x2 output pixels into out[y/2][x/2] (dgrad of a nearest x2 upsample); then no
-                                   bias / forward act / residual, act 3/4 read res1 at the half-resolution pixel */
+                                   bias / forward act / residual, act 3/4 read res1 at the half-resolution pixel.
+                                   2: MaxPool2d(2,2) of the bf16 output (perceptual.py:16's VGG pools; inference only):
+                                   out[y/2][x/2] = max over the 2x2 window of bf16(relu(acc + bias)), stored into a buffer of
+                                   out_h/2 x out_w/2 pixels (out_cstride / out_coff address that one); the un-pooled map is
+                                   not written.  Needs act 2, a bias, out_mode 0, even out_h / out_w, up 1, stride 1 and no
+                                   res1 / res2 / aux / bn_part / ch_part; bit-identical to the conv followed by
+                                   climsr_maxpool2_bf16.  Only the 64 -> 64 register-resident conv and the LDS-DMA conv have
+                                   it: climsr_conv2d_fwd_kernel answers "" for every other conv, which then returns
+                                   CLIMSR_EINVAL and writes nothing */
   int32_t res_f32;              /* bit 0: res1 is fp32, bit 1: res2 is fp32 */
   float beta1, beta2;           /* residual scales (1 for a plain residual add) */
   int32_t aux_cstride;
@@ -177,7 +185,8 @@ int climsr_conv2d_fwd(const ClimsrConvDesc* d, const uint16_t* x, const uint16_t
  * its dispatch cannot produce them (then bn_part must be NULL). */
 int64_t climsr_conv2d_fwd_bn_parts(const ClimsrConvDesc* d, const ClimsrEpilogue* ep);
 /* Name of the kernel climsr_conv2d_fwd launches for these arguments (as rocprof reports it; "" if invalid).
- * Launches nothing; used to label per-kernel timings and PMC traffic. */
+ * Launches nothing and needs no device; used to label per-kernel timings and PMC traffic, and to ask whether an
+ * optional epilogue (ep->down2 == 2) is taken: "conv_wr_kernel<5>" / "conv_fwd_dma_kernel<11, false>", or "". */
 const char* climsr_conv2d_fwd_kernel(const ClimsrConvDesc* d, const float* bias, const ClimsrEpilogue* ep);
 /* Kernel-name queries (profiler labels straight from the dispatch's route; nothing is launched): the weight-gradient
  * kernel climsr_conv2d_wgrad would launch for d (with climsr_conv2d_wgrad_splits(d) splits), and the data-gradient
