@@ -192,6 +192,9 @@ SIGNATURES = {
                                         c_void_p]),
     "climsr_maxpool2_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "climsr_l1_loss_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "climsr_l1_sign_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "climsr_maxpool2_relu_bwd_bf16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "climsr_sum3_scale_f32": (c_int, [c_void_p, c_int64, c_void_p, c_float, c_int64, c_void_p, c_void_p]),
     "climsr_f32_to_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "climsr_bn_inference": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_float,
                                     c_void_p, c_void_p]),

@@ -1289,6 +1289,112 @@ extern "C" int climsr_l1_loss_bf16(const uint16_t* a, const uint16_t* b, int64_t
   return check_launch("l1_loss_bf16");
 }
 
+// ---------------------------------------------------------------------------------------------
+// Backward of the perceptual term (losses/perceptual.py, differentiable=True): the L1 seed, the pool + ReLU routing
+// and the input end.  Gather forms: every output element is written exactly once, no atomics, no memset.
+// ---------------------------------------------------------------------------------------------
+union Bf8 {
+  uint4 v;
+  uint16_t h[8];
+};
+
+// out = sign(a - b) in {-1, 0, +1} as bf16: the compare is exact (a subtraction could flush a tiny difference to 0)
+__global__ void l1_sign_bf16_kernel(const uint16_t* __restrict__ a, const uint16_t* __restrict__ b, long n8, uint16_t* __restrict__ out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n8) return;
+  float fa[8], fb[8];
+  unpack8(((const uint4*)a)[i], fa);
+  unpack8(((const uint4*)b)[i], fb);
+  Bf8 o;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) o.h[q] = fa[q] > fb[q] ? 0x3F80 : (fa[q] < fb[q] ? 0xBF80 : 0);
+  ((uint4*)out)[i] = o.v;
+}
+
+extern "C" int climsr_l1_sign_bf16(const uint16_t* a, const uint16_t* b, int64_t n, uint16_t* out, void* stream) {
+  if (!a || !b || !out || n <= 0 || n % 8) {
+    set_error("l1_sign_bf16: bad args");
+    return CLIMSR_EINVAL;
+  }
+  hipLaunchKernelGGL(l1_sign_bf16_kernel, dim3(ceil_div((long)(n / 8), 256)), dim3(256), 0, (hipStream_t)stream, a, b, (long)(n / 8), out);
+  return check_launch("l1_sign_bf16");
+}
+
+// One lane = one 2x2 window x 8 channels: dz = gp at the window's first maximum of y in row-major order (0,0), (0,1),
+// (1,0), (1,1) (torch's CPU MaxPool2d rule) where that maximum is > 0 (the ReLU before the pool), 0 at the other three
+// and for an all-zero window.  144 B per lane: 4 x 16 B of y and 16 B of gp read, 4 x 16 B of dz written.
+__global__ void maxpool2_relu_bwd_kernel(const uint16_t* __restrict__ gp, const uint16_t* __restrict__ y, int n, int h, int w, int c,
+                                         uint16_t* __restrict__ dz) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int oh = h / 2, ow = w / 2, groups = c / 8;
+  const long total = (long)n * oh * ow * groups;
+  if (idx >= total) return;
+  const int cg = (int)(idx % groups);
+  long t = idx / groups;
+  const int j = (int)(t % ow);
+  t /= ow;
+  const int i = (int)(t % oh);
+  const int b = (int)(t / oh);
+  long off[4];
+  float f[4][8];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    off[r] = (((long)b * h + 2 * i + (r >> 1)) * w + 2 * j + (r & 1)) * c + cg * 8;
+    unpack8(*(const uint4*)(y + off[r]), f[r]);
+  }
+  Bf8 g, o[4];
+  g.v = *(const uint4*)(gp + (((long)b * oh + i) * ow + j) * c + cg * 8);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    int arg = 0;
+    float m = f[0][q];
+#pragma unroll
+    for (int r = 1; r < 4; ++r)
+      if (f[r][q] > m) {
+        m = f[r][q];
+        arg = r;
+      }
+    const bool pass = m > 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[r].h[q] = (pass && arg == r) ? g.h[q] : (uint16_t)0;
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) *(uint4*)(dz + off[r]) = o[r].v;
+}
+
+extern "C" int climsr_maxpool2_relu_bwd_bf16(const uint16_t* gp, const uint16_t* y, int n, int h, int w, int c, uint16_t* dz,
+                                             void* stream) {
+  if (!gp || !y || !dz || n <= 0 || h <= 0 || w <= 0 || c <= 0 || c % 8 || h % 2 || w % 2) {
+    set_error("maxpool2_relu_bwd_bf16: bad args");
+    return CLIMSR_EINVAL;
+  }
+  const long total = (long)n * (h / 2) * (w / 2) * (c / 8);
+  hipLaunchKernelGGL(maxpool2_relu_bwd_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, gp, y, n, h, w, c, dz);
+  return check_launch("maxpool2_relu_bwd_bf16");
+}
+
+// out[p] = (x[p][0] + x[p][1] + x[p][2]) * sign * gscale[0] / numel: the three input-channel gradients of cat([x, x, x])
+// summed, times the incoming 0-d gradient (device memory) and the mean's 1 / numel, all in fp32.  x rows of 4 floats.
+__global__ void sum3_scale_f32_kernel(const float* __restrict__ x, long npix, const float* __restrict__ gscale, float sign, float numel,
+                                      float* __restrict__ out) {
+  const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= npix) return;
+  const float s = sign * gscale[0] / numel;
+  const float4 v = ((const float4*)x)[p];
+  out[p] = ((v.x + v.y) + v.z) * s;
+}
+
+extern "C" int climsr_sum3_scale_f32(const float* x, int64_t npix, const float* gscale, float sign, int64_t numel, float* out,
+                                     void* stream) {
+  if (!x || !gscale || !out || npix <= 0 || numel <= 0) {
+    set_error("sum3_scale_f32: bad args");
+    return CLIMSR_EINVAL;
+  }
+  hipLaunchKernelGGL(sum3_scale_f32_kernel, dim3(ceil_div((long)npix, 256)), dim3(256), 0, (hipStream_t)stream, x, (long)npix, gscale,
+                     sign, (float)numel, out);
+  return check_launch("sum3_scale_f32");
+}
+
 // bf16 copy of an fp32 matrix (the fc.0 weight's MFMA copy), vectorised
 __global__ void f32_to_bf16_kernel(const float* __restrict__ x, long n, uint16_t* __restrict__ y) {
   long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 8;

@@ -703,6 +703,21 @@ def l1_bf16(a, b, n, ws, out):
     _launch("l1_bf16", lambda: _L().climsr_l1_loss_bf16(ptr(a), ptr(b), n, ptr(ws), ptr(out), _lib.stream_ptr()))
 
 
+def l1_sign_bf16(a, b, n, out):
+    _launch("l1_sign_bf16", lambda: _L().climsr_l1_sign_bf16(ptr(a), ptr(b), n, ptr(out), _lib.stream_ptr()), nbytes=6 * n)
+
+
+def maxpool2_relu_bwd(gp, y, n, h, w, c, dz):
+    """dz [n,h,w,c] from gp [n,h/2,w/2,c] and the stored un-pooled post-ReLU map y: 144 B per window x 8 channels."""
+    _launch("maxpool2_relu_bwd", lambda: _L().climsr_maxpool2_relu_bwd_bf16(ptr(gp), ptr(y), n, h, w, c, ptr(dz), _lib.stream_ptr()),
+            nbytes=n * (h // 2) * (w // 2) * (c // 8) * 144)
+
+
+def sum3_scale(x, npix, gscale, sign, numel, out):
+    _launch("sum3_scale", lambda: _L().climsr_sum3_scale_f32(ptr(x), npix, ptr(gscale), sign, numel, ptr(out), _lib.stream_ptr()),
+            nbytes=20 * npix)
+
+
 def f32_to_bf16(x, y):
     _launch("f32_to_bf16", lambda: _L().climsr_f32_to_bf16(ptr(x), x.numel(), ptr(y), _lib.stream_ptr()))
 

@@ -15,8 +15,11 @@ class GANLightningModule(TaskSuperResolutionModule):
         kwargs.setdefault("pixel_level_loss_factor", 0.01)       # conf/task/gan_training.yaml:6-8
         kwargs.setdefault("perceptual_loss_factor", 1.0)
         kwargs.setdefault("adversarial_loss_factor", 0.005)
+        # False = the reference (perceptual.py runs VGG under no_grad: the term is logged, G gets no gradient from it);
+        # True lets it train G (the published ESRGAN objective), see PerceptualLoss(differentiable=True)
+        kwargs.setdefault("differentiable_perceptual_loss", False)
         super().__init__(*args, **kwargs)
-        self.perceptual_criterion = PerceptualLoss()
+        self.perceptual_criterion = PerceptualLoss(differentiable=bool(self.hparams.differentiable_perceptual_loss))
         self.pixel_level_criterion = L1Loss()
 
     def _real_fake(self, size: int) -> Tuple[Tensor, Tensor]:

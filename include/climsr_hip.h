@@ -424,6 +424,16 @@ int climsr_relativistic_bce(const float* s_real, const float* s_fake, int n, flo
 int climsr_maxpool2_bf16(const uint16_t* x, int n, int h, int w, int c, uint16_t* y, void* stream);
 /* mean |a-b| over n bf16 elements (n % 8 == 0); workspace >= 512 doubles (perceptual.py:31-34). */
 int climsr_l1_loss_bf16(const uint16_t* a, const uint16_t* b, int64_t n, double* workspace, float* out, void* stream);
+/* Backward of the perceptual term (PerceptualLoss(differentiable=True)); all three write every output element once.
+ * out[i] = sign(a[i] - b[i]) as bf16 in {-1, 0, +1}, sign(0) = 0: the L1's gradient seed (n % 8 == 0). */
+int climsr_l1_sign_bf16(const uint16_t* a, const uint16_t* b, int64_t n, uint16_t* out, void* stream);
+/* Backward of ReLU + MaxPool2d(2,2) from the stored un-pooled post-ReLU map y [n][h][w][c]: dz [n][h][w][c] = gp
+ * [n][h/2][w/2][c] at each window's first maximum in row-major order where that maximum is > 0, else 0
+ * (c % 8 == 0, h and w even, as climsr_maxpool2_bf16). */
+int climsr_maxpool2_relu_bwd_bf16(const uint16_t* gp, const uint16_t* y, int n, int h, int w, int c, uint16_t* dz, void* stream);
+/* out[p] = (x[p][0] + x[p][1] + x[p][2]) * sign * gscale[0] / numel over npix rows of 4 floats: the gradient of
+ * cat([x, x, x]) with the incoming 0-d gradient (device scalar) and the mean's 1 / numel applied in fp32. */
+int climsr_sum3_scale_f32(const float* x, int64_t npix, const float* gscale, float sign, int64_t numel, float* out, void* stream);
 /* y = bf16(x) elementwise (MFMA copy of fp32 master weights). */
 int climsr_f32_to_bf16(const float* x, int64_t n, uint16_t* y, void* stream);
 
