@@ -91,6 +91,14 @@ class TileDesc(ctypes.Structure):
         (n, ctypes.c_int32) for n in ("method", "n", "h", "w", "scale", "lr_c", "srcnn", "use_elev", "use_mask")]
 
 
+class InferDesc(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("lr_raw", "lr_min", "lr_max", "lr_minmax", "elev_hr", "mask_hr", "elev_lr", "mask_lr",
+                                        "lr", "nearest", "out_min", "out_max")] + [
+        (n, c_double) for n in ("range_a", "range_b", "eps", "nan_sub", "zs_mean", "zs_std", "zs_nan_sub")] + [
+        (n, ctypes.c_int32) for n in ("method", "n", "h", "w", "hr_h", "hr_w", "scale", "lr_c", "srcnn", "use_elev", "use_mask",
+                                      "flip_ud")]
+
+
 SR_METRICS = 17
 
 
@@ -209,6 +217,9 @@ SIGNATURES = {
     "climsr_regression_accuracy_update": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p]),
     "climsr_denormalize_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_int, c_int64, c_void_p,
                                         c_void_p]),
+    "climsr_infer_static": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, c_float, c_double,
+                                    c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "climsr_infer_prepare": (c_int, [P(InferDesc), c_void_p]),
     "climsr_channel_attention_workspace": (c_size_t, [c_int, c_int]),
     "climsr_channel_attention": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                          c_void_p, c_void_p, c_void_p]),

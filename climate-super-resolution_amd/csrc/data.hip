@@ -14,6 +14,9 @@
 // block partials, single-block final sum) plus a separable-Gaussian SSIM pass.  Nothing syncs the
 // host: SSIM's data range and constants are read from the first pass's device results.
 //
+// Inference front end (end of the file): the same normalisation for whole raw LR grids plus the static
+// elevation / land-mask planes of the reference's two inference datasets.
+//
 // Built with -ffp-contract=off (Makefile): the normalisation reproduces numpy's one-rounding-per-
 // operation arithmetic bit for bit, which a fused multiply-add would break.
 #include <math.h>
@@ -117,29 +120,30 @@ __device__ __forceinline__ Scale32 minmax_f32_params(float mn, float mx, double 
   return {scale, add};
 }
 
+// StandardScaler._normalize: (arr - mean) / (std + eps) in float64 (np.float64 stats), rounded once.
+__device__ __forceinline__ float zscore_f64(float v, double mean, double std, double eps, double nan_sub) {
+  double r = __ddiv_rn(__dsub_rn((double)v, mean), __dadd_rn(std, eps));
+  float f = (float)r;
+  if (isnan(f) && nan_sub != 0.0) f = (float)nan_sub;  // `if self.nan_substitution:`
+  return f;
+}
+
+// `out_arr * scale; out_arr += min_` on a float32 array with float32 scale / offset, then NaN -> nan_sub.
+__device__ __forceinline__ float minmax_f32(float v, Scale32 s, float nan_sub) {
+  float f = __fadd_rn(__fmul_rn(v, s.mul), s.add);
+  return isnan(f) ? nan_sub : f;
+}
+
 __device__ __forceinline__ float normalize_hr(float v, const ClimsrTileDesc& d, double scale, double add) {
   if (d.method == 0) return minmax_f64(v, scale, add, (float)d.nan_sub);
-  if (d.method == 1) {  // StandardScaler: (arr - mean) / (std + eps) in float64 (np.float64 stats)
-    double r = __ddiv_rn(__dsub_rn((double)v, d.zs_hr_mean), __dadd_rn(d.zs_hr_std, d.eps));
-    float f = (float)r;
-    if (isnan(f) && d.zs_hr_nan_sub != 0.0) f = (float)d.zs_hr_nan_sub;  // `if self.nan_substitution:`
-    return f;
-  }
+  if (d.method == 1) return zscore_f64(v, d.zs_hr_mean, d.zs_hr_std, d.eps, d.zs_hr_nan_sub);
   return v;
 }
 
 __device__ __forceinline__ float normalize_elev(float v, const ClimsrTileDesc& d, Scale32 es) {
   if (v == d.elev_missing) v = NAN;  // `out_arr[arr == missing_indicator] = np.nan`
-  if (d.method == 0) {
-    float f = __fadd_rn(__fmul_rn(v, es.mul), es.add);
-    return isnan(f) ? (float)d.nan_sub : f;
-  }
-  if (d.method == 1) {
-    double r = __ddiv_rn(__dsub_rn((double)v, d.zs_elev_mean), __dadd_rn(d.zs_elev_std, d.eps));
-    float f = (float)r;
-    if (isnan(f) && d.zs_elev_nan_sub != 0.0) f = (float)d.zs_elev_nan_sub;
-    return f;
-  }
+  if (d.method == 0) return minmax_f32(v, es, (float)d.nan_sub);
+  if (d.method == 1) return zscore_f64(v, d.zs_elev_mean, d.zs_elev_std, d.eps, d.zs_elev_nan_sub);
   return v;
 }
 
@@ -769,4 +773,182 @@ extern "C" int climsr_denormalize_mask(const float* sr, const float* mask, const
   hipLaunchKernelGGL(denormalize_mask_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, sr, mask, min, max,
                      range_a, range_b, 1e-8, (long)hw, total, out);
   return check_launch("denormalize_mask");
+}
+
+// ------------------------------------------------------------------------------------------
+// Inference front end: GeoTiffInferenceDataset (geo_tiff_inference_dataset.py:74-96 once per dataset, :98-176 per
+// grid) and CRUTSInferenceDataset (cruts_inference_dataset.py:68-107).  Normalisation is element-wise, so the flip
+// and the nearest upscale are index maps applied on the way: one thread per HR output pixel reads its raw LR
+// pixel, normalises it and writes every output it owns.
+// ------------------------------------------------------------------------------------------
+namespace {
+constexpr long INFER_MAX_THREADS = 1L << 31;  // 2^23 workgroups of 256: block ids and ceil_div stay in int
+}
+
+// mask_hr = ~np.isnan(land); elev_hr = np.where(mask, elev, nan), the plane the nanmin / nanmax pass reads.
+__global__ void __launch_bounds__(256) infer_static_mask_kernel(const float* __restrict__ elev, const float* __restrict__ land,
+                                                                long total, float* __restrict__ elev_hr,
+                                                                float* __restrict__ mask_hr) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const bool is_land = !isnan(land[i]);
+  mask_hr[i] = is_land ? 1.f : 0.f;
+  elev_hr[i] = is_land ? elev[i] : NAN;
+}
+
+// elevation_scaler.normalize(masked, missing_indicator=...) in place, and the [::s, ::s] samples of both planes.
+__global__ void __launch_bounds__(256) infer_static_norm_kernel(float* __restrict__ elev_hr, const float* __restrict__ mask_hr,
+                                                                const float* __restrict__ minmax, int hr_h, int hr_w, int s,
+                                                                double a, double b, double eps, int method, float missing,
+                                                                double zs_mean, double zs_std, double zs_nan_sub,
+                                                                float* __restrict__ elev_lr, float* __restrict__ mask_lr) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)hr_h * hr_w) return;
+  const int y = (int)(i / hr_w), x = (int)(i - (long)y * hr_w);
+  float v = elev_hr[i];
+  if (v == missing) v = NAN;  // `out_arr[arr == missing_indicator] = np.nan`
+  if (method == 0) v = minmax_f32(v, minmax_f32_params(minmax[0], minmax[1], a, b, eps), 0.f);
+  else if (method == 1) v = zscore_f64(v, zs_mean, zs_std, eps, zs_nan_sub);
+  elev_hr[i] = v;
+  if (y % s == 0 && x % s == 0) {
+    const long lo = (long)(y / s) * (hr_w / s) + x / s;
+    elev_lr[lo] = v;
+    mask_lr[lo] = mask_hr[i];
+  }
+}
+
+extern "C" int climsr_infer_static(const float* elev_raw, const float* land_raw, int hr_h, int hr_w, int scale, double range_a,
+                                   double range_b, int method, float elev_missing, double zs_mean, double zs_std,
+                                   double zs_nan_sub, float* minmax, float* elev_hr, float* mask_hr, float* elev_lr,
+                                   float* mask_lr, void* stream) {
+  if (!elev_raw || !land_raw || !elev_hr || !mask_hr || !elev_lr || !mask_lr) {
+    set_error("infer_static: null pointer (elevation, land raster and the four output planes are required)");
+    return CLIMSR_EINVAL;
+  }
+  if (hr_h <= 0 || hr_w <= 0 || scale <= 0 || hr_h % scale || hr_w % scale) {
+    set_error("infer_static: %dx%d must be positive multiples of scale %d", hr_h, hr_w, scale);
+    return CLIMSR_EINVAL;
+  }
+  if (method < 0 || method > 2) {
+    set_error("infer_static: method %d outside 0..2", method);
+    return CLIMSR_EINVAL;
+  }
+  if (method == 0 && !minmax) {
+    set_error("infer_static: min-max normalisation needs the 2-float minmax scratch");
+    return CLIMSR_EINVAL;
+  }
+  if (elev_hr == elev_raw) {
+    set_error("infer_static: elev_hr stages the masked elevation and must not alias elev_raw");
+    return CLIMSR_EINVAL;
+  }
+  const long total = (long)hr_h * hr_w;
+  if (total > INFER_MAX_THREADS) {
+    set_error("infer_static: %dx%d pixels overflow one launch (limit 2^31)", hr_h, hr_w);
+    return CLIMSR_EINVAL;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(infer_static_mask_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, elev_raw, land_raw, total, elev_hr,
+                     mask_hr);
+  if (method == 0)
+    hipLaunchKernelGGL(tile_minmax_kernel, dim3(1), dim3(1024), 0, s, (const float*)elev_hr, total, elev_missing, 1, minmax);
+  hipLaunchKernelGGL(infer_static_norm_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, elev_hr, (const float*)mask_hr,
+                     (const float*)minmax, hr_h, hr_w, scale, range_a, range_b, 1e-8, method, elev_missing, zs_mean, zs_std,
+                     zs_nan_sub, elev_lr, mask_lr);
+  return check_launch("infer_static");
+}
+
+__global__ void __launch_bounds__(256) infer_prepare_kernel(ClimsrInferDesc d) {
+  const int hw = d.hr_h * d.hr_w;
+  long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long)d.n * hw) return;
+  const int t = (int)(gid / hw);
+  const int rem = (int)(gid - (long)t * hw);
+  const int y = rem / d.hr_w, x = rem - (rem / d.hr_w) * d.hr_w;
+  const int s = d.scale, ly = y / s, lx = x / s;
+  const int sy = d.flip_ud ? d.h - 1 - ly : ly;  // np.flipud(raw)
+  const float raw = d.lr_raw[((long)t * d.h + sy) * d.w + lx];
+
+  double mn = 0.0, mx = 0.0;  // what the grid is normalised with, as the batch's float64 min / max items
+  float v = raw;
+  if (d.lr_min) {  // scaler.normalize(img, min, max) with np.float64 min / max: float64, one rounding
+    mn = d.lr_min[t];
+    mx = d.lr_max[t];
+    if (d.method == 0) {
+      const double hs = __ddiv_rn(d.range_b - d.range_a, __dadd_rn(__dsub_rn(mx, mn), d.eps));
+      v = minmax_f64(raw, hs, __dsub_rn(d.range_a, __dmul_rn(mn, hs)), (float)d.nan_sub);
+    }
+  } else if (d.lr_minmax) {  // scaler.normalize(img): np.nanmin / np.nanmax of the float32 grid, float32 throughout
+    const float fmn = d.lr_minmax[2 * t], fmx = d.lr_minmax[2 * t + 1];
+    mn = (double)fmn;
+    mx = (double)fmx;
+    if (d.method == 0) v = minmax_f32(raw, minmax_f32_params(fmn, fmx, d.range_a, d.range_b, d.eps), (float)d.nan_sub);
+  }
+  if (d.method == 1) v = zscore_f64(raw, d.zs_mean, d.zs_std, d.eps, d.zs_nan_sub);
+  if (rem == 0 && (d.lr_min || d.lr_minmax)) {
+    d.out_min[t] = mn;
+    d.out_max[t] = mx;
+  }
+
+  d.nearest[(long)t * hw + rem] = v;  // nearest x s of the LR grid: out[y][x] = lr[y / s][x / s]
+  if (d.srcnn) {                      // _concat_if_needed, SRCNN branch: [nearest, elevation, mask] at HR size
+    float* l = d.lr + (long)t * d.lr_c * hw + rem;
+    int c = 0;
+    l[(long)(c++) * hw] = v;
+    if (d.use_elev) l[(long)(c++) * hw] = d.elev_hr[rem];
+    if (d.use_mask) l[(long)(c++) * hw] = d.mask_hr[rem];
+  } else if (ly * s == y && lx * s == x) {  // [lr, elevation_lr, mask_lr] at LR size
+    const int lhw = d.h * d.w, lo = ly * d.w + lx;
+    float* l = d.lr + (long)t * d.lr_c * lhw + lo;
+    int c = 0;
+    l[(long)(c++) * lhw] = v;
+    if (d.use_elev) l[(long)(c++) * lhw] = d.elev_lr[lo];
+    if (d.use_mask) l[(long)(c++) * lhw] = d.mask_lr[lo];
+  }
+}
+
+extern "C" int climsr_infer_prepare(const ClimsrInferDesc* d, void* stream) {
+  if (!d || !d->lr_raw || !d->lr || !d->nearest) {
+    set_error("infer_prepare: null pointer (desc, lr_raw, lr and nearest are required)");
+    return CLIMSR_EINVAL;
+  }
+  if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->scale <= 0 || (long)d->scale * d->h != d->hr_h ||
+      (long)d->scale * d->w != d->hr_w) {
+    set_error("infer_prepare: HR size %dx%d is not scale %d x the LR grid %dx%d (n=%d)", d->hr_h, d->hr_w, d->scale, d->h, d->w,
+              d->n);
+    return CLIMSR_EINVAL;
+  }
+  if (d->method < 0 || d->method > 2) {
+    set_error("infer_prepare: method %d outside 0..2", d->method);
+    return CLIMSR_EINVAL;
+  }
+  const int want_c = 1 + (d->use_elev ? 1 : 0) + (d->use_mask ? 1 : 0);
+  if (d->lr_c != want_c) {
+    set_error("infer_prepare: lr_c=%d, expected 1 + use_elev + use_mask = %d", d->lr_c, want_c);
+    return CLIMSR_EINVAL;
+  }
+  if ((d->lr_min == nullptr) != (d->lr_max == nullptr)) {
+    set_error("infer_prepare: lr_min and lr_max come together");
+    return CLIMSR_EINVAL;
+  }
+  const int routes = (d->lr_min ? 1 : 0) + (d->lr_minmax ? 1 : 0);
+  if (routes > 1 || (d->method == 0 && routes != 1)) {
+    set_error("infer_prepare: %d statistics routes given; min-max needs exactly one of lr_min / lr_max and lr_minmax", routes);
+    return CLIMSR_EINVAL;
+  }
+  if (routes && (!d->out_min || !d->out_max)) {
+    set_error("infer_prepare: null out_min / out_max (required with a statistics route)");
+    return CLIMSR_EINVAL;
+  }
+  if ((d->use_elev && !(d->srcnn ? d->elev_hr : d->elev_lr)) || (d->use_mask && !(d->srcnn ? d->mask_hr : d->mask_lr))) {
+    set_error("infer_prepare: null static plane (the %s elevation / mask of climsr_infer_static)", d->srcnn ? "HR" : "LR");
+    return CLIMSR_EINVAL;
+  }
+  const long hw = (long)d->hr_h * d->hr_w;
+  if (hw > 0x7fffffffL || d->n > INFER_MAX_THREADS / hw) {
+    set_error("infer_prepare: n=%d grids of %dx%d overflow one launch (limit 2^31 HR pixels); split the batch", d->n, d->hr_h,
+              d->hr_w);
+    return CLIMSR_EINVAL;
+  }
+  hipLaunchKernelGGL(infer_prepare_kernel, dim3(ceil_div(d->n * hw, 256)), dim3(256), 0, (hipStream_t)stream, *d);
+  return check_launch("infer_prepare");
 }

@@ -1,3 +1,4 @@
-"""On-device data pipeline: the per-sample work of the reference's
-``ClimateDataset`` done for a whole batch of raw tiles in HBM by ``libclimsr_hip.so``."""
+"""On-device data pipelines: the per-sample work of the reference's ``ClimateDataset`` for a
+whole batch of raw tiles, and of its two inference datasets for whole raw grids, in HBM by ``libclimsr_hip.so``."""
+from .inference_pipeline import DeviceInferencePipeline  # noqa: F401
 from .tile_pipeline import DeviceTilePipeline, TransformsCfg  # noqa: F401

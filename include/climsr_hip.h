@@ -521,6 +521,54 @@ int climsr_denormalize_mask(const float* sr, const float* mask, const double* mi
                             double range_b, int n, int64_t hw, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Inference front end: the per-dataset and per-grid CPU work of GeoTiffInferenceDataset
+ * (climsr/data/sr/geo_tiff_inference_dataset.py:74-96, 98-176) and CRUTSInferenceDataset
+ * (cruts_inference_dataset.py:68-107) for raw LR grids already in HBM.  Contiguous fp32 planes; hr_h == scale * h,
+ * hr_w == scale * w.  Same rounding contract as the tile pipeline (one rounding per numpy operation).
+ * --------------------------------------------------------------------------------------------- */
+/* Once per dataset, from the raw HR elevation and the raw HR land raster (NaN = sea), both [hr_h][hr_w]:
+ *   mask_hr = ~isnan(land);  elev_hr = normalise(where(mask, elev, NaN) with == elev_missing -> NaN), NaN -> 0;
+ *   elev_lr, mask_lr [hr_h/scale][hr_w/scale] = the [::scale, ::scale] samples (INTER_NEAREST, integer ratio).
+ * method 0: MinMaxScaler with the masked plane's own float32 nanmin / nanmax (float32 arithmetic); `minmax` is a
+ * 2-float device scratch that receives them.  method 1: float64 (v - zs_mean) / (zs_std + 1e-8) rounded once, NaN ->
+ * zs_nan_sub only if that is non-zero (as ClimsrTileDesc's elevation); method 2: the masked plane as it is.
+ * elev_hr is also the staging plane of the masked elevation: it must not alias elev_raw.  Three launches. */
+int climsr_infer_static(const float* elev_raw, const float* land_raw, int hr_h, int hr_w, int scale, double range_a,
+                        double range_b, int method, float elev_missing, double zs_mean, double zs_std, double zs_nan_sub,
+                        float* minmax, float* elev_hr, float* mask_hr, float* elev_lr, float* mask_lr, void* stream);
+
+typedef struct {
+  const float* lr_raw;       /* [n][h][w] raw LR grids (NaN = no data / sea) */
+  const double* lr_min;      /* lookup route: [n] float64 min / max (float64 arithmetic, one rounding), else NULL */
+  const double* lr_max;
+  const float* lr_minmax;    /* own-statistics route: [n][2] float32 nanmin / nanmax of each grid
+                                (climsr_tile_minmax_f32; float32 arithmetic), else NULL */
+  const float* elev_hr;      /* [hr_h][hr_w] planes of climsr_infer_static; the SRCNN layout reads the HR pair, */
+  const float* mask_hr;      /* the others the LR pair; each needed only with use_elev / use_mask */
+  const float* elev_lr;      /* [h][w] */
+  const float* mask_lr;
+  float* lr;                 /* [n][lr_c][h][w] = [norm, elev_lr, mask_lr]; SRCNN: [n][lr_c][hr_h][hr_w] =
+                                [nearest, elev_hr, mask_hr] */
+  float* nearest;            /* [n][1][hr_h][hr_w] nearest x scale of the normalised grid */
+  double* out_min;           /* [n] the min / max the grid was normalised with (lookup: copied; own statistics: */
+  double* out_max;           /* widened); required whenever a route is given */
+  double range_a, range_b;   /* MinMaxScaler feature_range */
+  double eps;                /* 1e-8 */
+  double nan_sub;            /* MinMaxScaler nan_substitution (0.0) */
+  double zs_mean, zs_std, zs_nan_sub;  /* method 1, as ClimsrTileDesc.zs_hr_* */
+  int32_t method;            /* 0 minmax (exactly one route), 1 zscore, 2 none (a route is optional: min / max only) */
+  int32_t n, h, w;           /* LR grid */
+  int32_t hr_h, hr_w;        /* == scale * h, scale * w */
+  int32_t scale;
+  int32_t lr_c;              /* 1 + use_elev + use_mask */
+  int32_t srcnn, use_elev, use_mask;
+  int32_t flip_ud;           /* np.flipud of each raw grid first (both reference datasets do) */
+} ClimsrInferDesc;
+
+/* flip / normalise / NaN -> nan_sub / nearest upscale / concat for n grids.  One launch, one thread per HR pixel. */
+int climsr_infer_prepare(const ClimsrInferDesc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * RCAN (climsr/models/rcan.py).
  * --------------------------------------------------------------------------------------------- */
 /* CALayer (rcan.py:50-69): s[n][c] = sigmoid(w2 . relu(w1 . mean_p u[n][p][:] + b1) + b2), u fp32 NHWC
